@@ -14,13 +14,21 @@ N>1: one process per GPU, every rank restores its own batch of 8 (weak scaling),
 all_gather of the restored images at the end of each step (inside the timed region).
 Prints ONE JSON line on rank 0.  Started WITHOUT torchrun, `--gpus N > 1` re-executes itself under
 `torch.distributed.run --nproc-per-node N` (exit code 2 when fewer than N devices are visible); the line
-carries `backend`, `ranks_seen` and the per-rank step-time spread, and at N > 1 it appends configs[2] /
-configs[3] with their fixed GLOBAL batch split over the ranks (`--no-extra-workloads` skips them).
+carries `backend`, `ranks_seen` and the per-rank step-time spread.
 
-At 1 GPU the default run appends `"workloads": {"c3", "c4", "c5"}`: the per-GPU shards of BASELINE configs[2..4]
-(ImageNet ADM UNet in the runner's fp16 mode), 1 warm-up + 2 timed restorations each, each with its own
-`roofline` against the 2.5 PFLOP/s fp16 MFMA peak (`--no-extra-workloads` skips them; `--workload c3 --scaling
-strong` times configs[2] / configs[3] with their fixed GLOBAL batch of 32 / 16 split over the ranks).
+A plain run does only what the headline figure needs: set-up, `--warmup` passes, `--steps` timed passes, the
+outputs of the last timed pass when `--dump-outputs DIR` is given (`DIR/restored.npy`, float32, the gathered
+restorations a caller of the path receives), and the result line.  Everything else is measured or checked only
+with `--full`:
+  * the data-consistency and finiteness checks of the last pass and the timed all_gather alone (`gather_ms`);
+  * `roofline` / `roofline_hbm` / `precision_check` (instrumented passes, profiles bound by source digest);
+  * `latency` (B = 1 / 2, eager and graph) and `f32_mfma_path` (the all-fp32-MFMA engine), skipped by --no-side-path;
+  * `workloads`: at 1 GPU the per-GPU shards of BASELINE configs[2..4] (ImageNet ADM UNet in the runner's fp16 mode,
+    1 warm-up + 2 timed restorations each, each with its own `roofline` against the 2.5 PFLOP/s fp16 MFMA peak); at
+    N > 1 configs[2] / configs[3] with their fixed GLOBAL batch split over the ranks (--no-extra-workloads skips them);
+  * `cpu_baseline`: the reference path on the host cores (--no-cpu-baseline skips it).
+`--workload c3 --scaling strong` times configs[2] / configs[3] with their fixed GLOBAL batch of 32 / 16 split over
+the ranks.
 """
 import argparse
 import json
@@ -224,11 +232,21 @@ def real_inpainting_mask():
     return torch.from_numpy(bits.reshape(shape).astype(np.int64))
 
 
-def adm_workload(name, ddist, rank, world, dev, steps, warmup, strong=False, roofline=True, lib_digest=None):
+def dump_outputs(dump_dir, **arrays):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32 (what the timed path hands its caller)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, f"{name}.npy"), a.detach().float().cpu().numpy())
+
+
+def adm_workload(name, ddist, rank, world, dev, steps, warmup, strong=False, roofline=True, lib_digest=None, full=True,
+                 dump_dir=None):
     """One ImageNet workload: ADM UNet (552.81 M parameters, 2242.87 GFLOP per forward per image) in the runner's
     `use_fp16: true` mode = fp16 activations + fp16 MFMA operands, fp32 accumulation (ddnm_amd/guided_diffusion/unet.py).
     weak scaling (default): every rank restores the per-GPU shard of the BASELINE config; `strong`: the config's GLOBAL
-    batch is split over the ranks present.  Returns the result dict (rank 0 prints it)."""
+    batch is split over the ranks present.  `full = False` (a plain `--workload` run) leaves out the launch count of the
+    classifier and the finiteness check.  Returns the result dict (rank 0 prints it)."""
     import types
     from ddnm_amd import ops
     from ddnm_amd.functions.svd_ddnm import ddnm_diffusion, get_schedule_jump
@@ -261,16 +279,17 @@ def adm_workload(name, ddist, rank, world, dev, steps, warmup, strong=False, roo
                              for k, v in clf.state_dict_shapes().items()})
         clf.convert_to_fp16()                  # imagenet_256_cc.yml: classifier_use_fp16 true
         cls_fn = make_cond_fn(clf, 1.0)
-        try:        # FLOPs of one guidance evaluation, counted from the launches of one instrumented call
-            ctimer = ops.KernelTimer()
-            ops.set_kernel_timer(ctimer)
-            xx = torch.randn(2, 3, 256, 256, device=dev)
-            cls_fn(xx, torch.full((2,), 500.0, device=dev), torch.full((2,), 951, dtype=torch.long, device=dev))
-            ops.set_kernel_timer(None)
-            torch.cuda.synchronize()
-            cls_flops_per_image = sum(f for _, f, _, _ in ctimer.records) / 2.0
-        except Exception:      # noqa: BLE001
-            ops.set_kernel_timer(None)
+        if full:
+            try:        # FLOPs of one guidance evaluation, counted from the launches of one instrumented call
+                ctimer = ops.KernelTimer()
+                ops.set_kernel_timer(ctimer)
+                xx = torch.randn(2, 3, 256, 256, device=dev)
+                cls_fn(xx, torch.full((2,), 500.0, device=dev), torch.full((2,), 951, dtype=torch.long, device=dev))
+                ops.set_kernel_timer(None)
+                torch.cuda.synchronize()
+                cls_flops_per_image = sum(f for _, f, _, _ in ctimer.records) / 2.0
+            except Exception:      # noqa: BLE001
+                ops.set_kernel_timer(None)
     betas = torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=0.02,
                                                num_diffusion_timesteps=1000)).float().to(dev)
     if strong:
@@ -316,6 +335,8 @@ def adm_workload(name, ddist, rank, world, dev, steps, warmup, strong=False, roo
     ddist.barrier()
     dt_rank = time.perf_counter() - t0
     dt, dt_min = ddist.reduce_scalar(dt_rank, dev, "max"), ddist.reduce_scalar(dt_rank, dev, "min")
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, restored=out)
     value = steps * n_total / dt
     per_step = ADM_FLOPS_PER_FWD
     if name == "c5":
@@ -333,8 +354,9 @@ def adm_workload(name, ddist, rank, world, dev, steps, warmup, strong=False, roo
                       "reproduces_baseline_config": bool(world == W["ranks"] and (strong or W["ranks"] == 1)),
                       "variant": (None if world == W["ranks"] or not strong else
                                   f"BASELINE global batch {W['global_batch']} on {world} ranks instead of {W['ranks']}")},
-           "whole_loop_tflops_per_gpu": round(tfl, 1), "whole_loop_frac": round(tfl / PEAK_F16_TFLOPS, 4),
-           "finite": bool(torch.isfinite(out).all())}
+           "whole_loop_tflops_per_gpu": round(tfl, 1), "whole_loop_frac": round(tfl / PEAK_F16_TFLOPS, 4)}
+    if full:
+        res["finite"] = bool(torch.isfinite(out).all())
     if name == "c5":
         res["classifier_gflop_per_image_step"] = round((cls_flops_per_image or CLS_FLOPS_ESTIMATE) / 1e9, 1)
         res["classifier_flops_source"] = ("counted from the launches of one guidance evaluation (convolutions, batched "
@@ -497,13 +519,22 @@ def main():
                          "0.25 + classifier guidance (ADM UNet in the runner's use_fp16 mode)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="c3 / c4 only: strong = the BASELINE config's global batch (32 / 16) split over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, run every other measurement and check (consistency, gather_ms, "
+                         "roofline, precision_check, latency, f32_mfma_path, the appended workloads, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/restored.npy (float32; "
+                         "e.g. DIR = bench_outputs)")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="default c2 run at 1 GPU: do not append the short c3 / c4 / c5 measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="--full c2 run: do not append the short c3 / c4 / c5 measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the instrumented roofline / precision passes")
     ap.add_argument("--no-side-path", action="store_true",
-                    help="skip the one-pass measurement of the all-fp32-MFMA engine (kernel-trace profiles of the headline path)")
+                    help="--full: skip the one-pass measurement of the all-fp32-MFMA engine (kernel-trace profiles of the "
+                         "headline path)")
     args = ap.parse_args()
+    if not args.full:              # a plain run measures the headline figure only
+        args.no_extra_workloads = args.no_cpu_baseline = args.no_roofline = args.no_side_path = True
 
     from ddnm_amd import _lib
     from ddnm_amd import dist as ddist
@@ -531,7 +562,8 @@ def main():
     cfg = make_config()
     if args.workload != "c2":
         res = adm_workload(args.workload, ddist, rank, world, dev, args.steps, args.warmup,
-                           strong=(args.scaling == "strong"), roofline=not args.no_roofline, lib_digest=lib_digest)
+                           strong=(args.scaling == "strong"), roofline=not args.no_roofline, lib_digest=lib_digest,
+                           full=args.full, dump_dir=args.dump_outputs)
         line = {"metric": "restored images/sec @256x256, 100 DDIM steps", "higher_is_better": True, "vs_baseline": None,
                 "library_digest": lib_digest[:16]}
         line.update(res)
@@ -580,30 +612,19 @@ def main():
     ddist.barrier()
     dt_rank = time.perf_counter() - t0
     dt, dt_min = ddist.reduce_scalar(dt_rank, dev, "max"), ddist.reduce_scalar(dt_rank, dev, "min")
-    assert out.shape[0] == B * world and bool(torch.isfinite(out).all())
-    # data-consistency spot check of the last pass (this rank's slice): A x_0 = y
-    mine = out[rank * B:(rank + 1) * B]
-    resid = (op.A(mine) - y).abs().max().item()
-
-    # the path's single collective on its own: the all_gather of the restored images (inside every timed step above),
-    # timed over 5 repetitions after the timed region, slowest rank
-    ddist.barrier()
-    torch.cuda.synchronize()
-    tg = time.perf_counter()
-    for _ in range(5):
-        ddist.gather_images(mine.contiguous())
-    torch.cuda.synchronize()
-    gather_ms = ddist.reduce_scalar((time.perf_counter() - tg) / 5 * 1e3, dev, "max")
+    assert out.shape[0] == B * world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, restored=out)
     value = args.steps * B * world / dt
     line = {
         "metric": baseline_metric(), "value": round(value, 4),
         "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(dt / args.steps * 1e3, 2), "ms_per_step_rank_min": round(dt_min / args.steps * 1e3, 2),
         "higher_is_better": True, "scaling": "weak", "backend": dist_info["backend"], "ranks_seen": ranks_seen,
-        "startup_s": round(startup_s, 2), "gather_ms": round(gather_ms, 3),
+        "startup_s": round(startup_s, 2),
         "timing_note": "startup_s = process start -> ready to sample (imports, library load, process group, weight packing), "
-                       "slowest rank, NOT in the timed region; gather_ms = the single all_gather of one step's restored images "
-                       "(part of every timed step), slowest rank; ms_per_step = steady state incl. that gather",
+                       "slowest rank, NOT in the timed region; ms_per_step = steady state incl. the all_gather of one "
+                       "step's restored images",
         "vs_baseline": None,
         "dtype": ("f32 (3x3 convolutions: fp32 operands carried as hi + lo fp16 halves, three fp16 MFMA products per "
                   "product, fp32 accumulate -- operand error 2^-22, measured closer to fp64 than the fp32 MFMA kernel; "
@@ -613,8 +634,23 @@ def main():
         "config": {"workload": "celeba_hq.yml SVD sr_bicubic 4x, sigma_y=0, eta=0.85, T_sampling=100, "
                                "batch_size=8 per GPU (BASELINE configs[1])",
                    "global_batch": B * world, "image": "3x256x256", "parallelism": f"dp{world} (image sharding)"},
-        "consistency_max_abs": resid, "library_digest": lib_digest[:16],
+        "library_digest": lib_digest[:16],
     }
+    if args.full:
+        assert bool(torch.isfinite(out).all())
+        # data-consistency spot check of the last pass (this rank's slice): A x_0 = y
+        mine = out[rank * B:(rank + 1) * B]
+        line["consistency_max_abs"] = (op.A(mine) - y).abs().max().item()
+        # the path's single collective on its own: the all_gather of the restored images (inside every timed step
+        # above), timed over 5 repetitions after the timed region, slowest rank
+        ddist.barrier()
+        torch.cuda.synchronize()
+        tg = time.perf_counter()
+        for _ in range(5):
+            ddist.gather_images(mine.contiguous())
+        torch.cuda.synchronize()
+        line["gather_ms"] = round(ddist.reduce_scalar((time.perf_counter() - tg) / 5 * 1e3, dev, "max"), 3)
+        line["timing_note"] += "; gather_ms = that all_gather alone, slowest rank"
 
     if rank == 0 and not args.no_roofline:
         try:                      # the headline line must be printed even if the instrumented pass fails
@@ -770,7 +806,8 @@ def main():
         for wname, strong, nsteps in plan:
             try:                       # every rank takes part (collectives inside); a failure must not cost the line
                 line["workloads"][wname] = adm_workload(wname, ddist, rank, world, dev, nsteps, 1, strong=strong,
-                                                        roofline=not args.no_roofline, lib_digest=lib_digest)
+                                                        roofline=not args.no_roofline, lib_digest=lib_digest,
+                                                        full=args.full)
             except Exception as e:    # noqa: BLE001
                 line["workloads"][wname] = {"error": repr(e)}
         if done is not None:

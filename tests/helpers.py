@@ -1,6 +1,18 @@
 """Shared helpers of the GPU parity tests."""
+import glob
+import os
+
 import numpy as np
 import torch
+
+
+def load_npz(path):
+    """A golden .npz as a dict, merged with its continuation files `<stem>.part<k>.npz`: a fixture larger than a
+    committed file may be is split by keys (tests/golden/make_golden.py::save_npz)."""
+    out = dict(np.load(path))
+    for part in sorted(glob.glob(glob.escape(path[:-len(".npz")]) + ".part*.npz")):
+        out.update(np.load(part))
+    return out
 
 
 def real_mask(golden_dir):

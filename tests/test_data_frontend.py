@@ -1,17 +1,19 @@
 """Image front-end against tests/golden/data_frontend.json -- what the REFERENCE's dataset code
-(its own `center_crop_arr` and `CenterCropLongEdge`, imported from /root/reference; torchvision's Resize / ToTensor restated
-as the PIL / numpy calls they are for PIL images, tests/golden/make_golden_data.py) makes of the 8 + 8 images under
-exp/datasets.  The images live in the reference tree only, so the comparison runs where /root/reference exists (the build
-container); everywhere the fixture itself is checked for shape."""
+(its own `center_crop_arr` and `CenterCropLongEdge`; torchvision's Resize / ToTensor restated as the PIL / numpy calls they
+are for PIL images, tests/golden/make_golden_data.py) makes of the 8 + 8 images under exp/datasets.  The 8 ImageNet samples
+are committed under tests/golden/images/; the 8 CelebA-HQ faces (1024 x 1024 PNGs, too large to commit) are represented by
+their central 320 x 320 crops under tests/golden/images/celeba_hq_crop320/, with their own fixture
+tests/golden/data_frontend_celeba_crop320.json (tests/golden/make_golden_ref_pins.py)."""
 import hashlib
 import json
 import os
+import shutil
 
 import numpy as np
 import pytest
 
-REF = "/root/reference/exp/datasets"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IMAGES = os.path.join(ROOT, "tests", "golden", "images")
 
 
 @pytest.fixture(scope="module")
@@ -33,15 +35,22 @@ def _check(x, ent, name):
     assert hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest() == ent["sha256"], name
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's sample images are not on this machine")
 def test_engine_front_end_reproduces_the_reference_pipeline(golden, tmp_path):
     from ddnm_amd.guided_diffusion.diffusion import ImageFolder, ImageList
+    # the reference's exp/datasets layout, from the committed samples
+    REF = tmp_path / "datasets"
+    shutil.copytree(os.path.join(IMAGES, "celeba_hq_crop320"), REF / "celeba_hq")
+    os.makedirs(REF / "imagenet" / "imagenet")
+    for n in golden["imagenet_center_crop_arr"]:
+        shutil.copy(os.path.join(IMAGES, n), REF / "imagenet" / "imagenet" / n)
+    crops = json.load(open(os.path.join(ROOT, "tests", "golden", "data_frontend_celeba_crop320.json")))
+    assert sorted(crops) == sorted(golden["celeba_hq"])                                  # the same 8 faces
     ds = ImageFolder(os.path.join(REF, "celeba_hq"), 256, transform="resize")            # CelebA_HQ / FFHQ branch
     assert len(ds) == 8
     for i in range(8):
         x, cls = ds[i]
         assert cls == 0 and x.shape == (3, 256, 256) and 0.0 <= float(x.min()) and float(x.max()) <= 1.0
-        _check(x, golden["celeba_hq"][os.path.basename(ds.items[i][0])], ds.items[i][0])
+        _check(x, crops[os.path.basename(ds.items[i][0])], ds.items[i][0])
     ds = ImageFolder(os.path.join(REF, "imagenet"), 256, transform="center_crop_arr")    # ImageNet / out_of_dist branch
     for i in range(len(ds)):
         x, _ = ds[i]

@@ -190,7 +190,7 @@ def test_bench_self_launches_ranks_from_a_plain_command(hip):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DDNM_DIST_BACKEND="gloo", PYTHONPATH=root)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--no-extra-workloads", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True,
+                        "--full", "--no-extra-workloads", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -247,7 +247,7 @@ def test_bench_eight_ranks_on_one_gpu(hip):
     env.update(DDNM_DIST_BACKEND="gloo", PYTHONPATH=root)
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=1700)
+                        "--full", "--no-cpu-baseline", "--no-roofline"], env=env, capture_output=True, text=True, timeout=1700)
     wall = time.time() - t0
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -275,7 +275,7 @@ def test_bench_four_ranks_reproduce_baseline_config3(hip):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DDNM_DIST_BACKEND="gloo", PYTHONPATH=root)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--workload", "c4", "--scaling", "strong",
-                        "--steps", "1", "--warmup", "0", "--no-roofline"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--steps", "1", "--warmup", "0", "--full", "--no-roofline"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert line["n_gpus"] == 4 and line["ranks_seen"] == 4 and line["config"]["global_batch"] == 16

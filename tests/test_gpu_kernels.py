@@ -344,7 +344,7 @@ def test_operator_svd_surface(hip, name, golden_dir):
     the reference base class derives them; then the reference's own outputs (tests/golden/spectral.npz, every 5th
     entry): exact orderings for the permutation-type operators, and the basis-independent products for the operators
     built on a LAPACK SVD (their V_small columns are unique only up to sign / rotation of degenerate subspaces)."""
-    from tests.helpers import engine_operator
+    from tests.helpers import engine_operator, load_npz
     d, B = 64, 2
     op = engine_operator(name, d)
     from oracle import cases
@@ -369,7 +369,7 @@ def test_operator_svd_surface(hip, name, golden_dir):
         assert rel(op.A_pinv_eta(w, 0.0), op.A_pinv(w)) < 2e-5
     if name == "denoising":
         return
-    gold = np.load(f"{golden_dir}/spectral.npz")
+    gold = load_npz(f"{golden_dir}/spectral.npz")
     gz, gw = torch.from_numpy(gold[f"{name}_z"]).cuda(), torch.from_numpy(gold[f"{name}_w"]).cuda()
     sp = lambda t: t[:, ::5].cpu()                                          # noqa: E731
     assert rel(sp(op.At(gw)), torch.from_numpy(gold[f"{name}_At"])) < 2e-5

@@ -163,11 +163,11 @@ def test_every_reference_config_has_a_counterpart():
     for n in names:
         cfg = yaml.safe_load(open(os.path.join(root, "configs", n)))
         assert {"model", "diffusion", "data", "sampling", "time_travel"} <= set(cfg), n
-    ref_dir = "/root/reference/configs"
-    if os.path.isdir(ref_dir):
-        assert sorted(os.listdir(ref_dir)) == names
-        for n in names:
-            assert yaml.safe_load(open(os.path.join(root, "configs", n))) == yaml.safe_load(open(os.path.join(ref_dir, n))), n
+    # the reference's configs/*.yml, parsed (tests/golden/reference_configs.json, tests/golden/make_golden_ref_pins.py)
+    ref = json.load(open(os.path.join(root, "tests", "golden", "reference_configs.json")))
+    assert sorted(ref) == names
+    for n in names:
+        assert yaml.safe_load(open(os.path.join(root, "configs", n))) == ref[n], n
 
 
 def test_respaced_betas_keep_only_integer_timesteps():

@@ -1,13 +1,15 @@
 """CPU tests: the oracle restatement against the golden vectors produced by the REAL reference
-(tests/golden/make_golden.py), plus -- where /root/reference exists (build container only) --
-a direct comparison with the imported reference.  No GPU, no HIP calls."""
+(tests/golden/make_golden.py), plus direct pins against what the reference computes on the same seeded inputs
+(recorded in tests/golden/reference_pins.npz by tests/golden/make_golden_ref_pins.py).  No GPU, no HIP calls."""
+import hashlib
 import json
+import os
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import cases, ref_import, sampler, schedule, unet_celeba, weights
+from oracle import cases, sampler, schedule, unet_celeba, weights
 from tests.helpers import real_mask, rel
 
 OPS = ["sr_averagepooling", "sr_bicubic", "colorization", "inpainting", "cs_walshhadamard", "denoising"]
@@ -105,71 +107,49 @@ def test_full_c2_golden_metadata(golden_dir):
     assert float(g["ref_cpu_seconds"][0]) > 10
 
 
-# ---- direct pins against the imported reference (build container only) -------------------------------
-needs_ref = pytest.mark.skipif(not ref_import.available(), reason="/root/reference not present on this box")
+# ---- direct pins against what the reference computes (tests/golden/make_golden_ref_pins.py) -----------------
+@pytest.fixture(scope="module")
+def ref_pins(golden_dir):
+    return np.load(os.path.join(golden_dir, "reference_pins.npz"))
 
 
-@needs_ref
-def test_reference_unet_bit_identical():
-    ns = ref_import.load()
+def _digest(obj):
+    """The 8-byte digest make_golden_ref_pins.py stores for each reference schedule result (numbers by value)."""
+    key = obj if isinstance(obj, str) else [float(v) for v in obj]
+    return int.from_bytes(hashlib.blake2b(repr(key).encode(), digest_size=8).digest(), "little")
+
+
+def test_reference_unet_bit_identical(ref_pins):
     cfg, sd = cases.celeba_net("small")
-    ref = ns.models.Model(cfg)
-    ref.load_state_dict(sd)
-    ref.eval()
     x, t = cases.forward_inputs(cfg, 2, seed=7)
-    with torch.no_grad():
-        a = ref(x, t)
+    a = torch.from_numpy(ref_pins["unet_small_eps_seed7"])                 # the reference's Model(cfg) on (x, t)
     assert torch.equal(a, unet_celeba.Net(sd, cfg)(x, t))
 
 
-@needs_ref
-def test_reference_sampler_direct():
-    ns = ref_import.load()
+def test_reference_sampler_direct(ref_pins):
     cfg, sd = cases.celeba_net("small")
     cfg.time_travel.T_sampling, cfg.time_travel.travel_length, cfg.time_travel.travel_repeat = 10, 1, 1
-    ref = ns.models.Model(cfg)
-    ref.load_state_dict(sd)
-    ref.eval()
     x_orig, x_T, tape = cases.sampler_case(cfg, 1, 10, seed=11)
-    op_ref = ns.svd_operators.SuperResolution(3, 32, 4, "cpu")
     op = cases.make_operator("sr_averagepooling", 32)
-    y = op_ref.A(x_orig)
-    with ref_import.cuda_is_cpu(), ref_import.noise_tape(tape):
-        xs, x0s = ns.svd_ddnm.ddnm_diffusion(x_T.clone(), ref, cases.betas(), 0.85, op_ref, y, cls_fn=None,
-                                             classes=None, config=cfg)
+    y = torch.from_numpy(ref_pins["sampler_direct_y"])                   # the reference's SuperResolution(3, 32, 4).A
+    assert torch.equal(op.A(x_orig), y)
+    # the reference's ddnm_diffusion with its own Model and operator, the same noise tape
+    xs0, x0s0 = torch.from_numpy(ref_pins["sampler_direct_x"]), torch.from_numpy(ref_pins["sampler_direct_x0"])
     x, x0 = sampler.ddnm_diffusion(x_T.clone(), unet_celeba.Net(sd, cfg), cases.betas(), 0.85, op, y, tape,
                                    T_sampling=10)
-    assert rel(x, xs[0]) < 1e-5 and rel(x0, x0s[0]) < 1e-5
+    assert rel(x, xs0) < 1e-5 and rel(x0, x0s0) < 1e-5
 
 
-@needs_ref
-def test_reference_simplified_loop_restatement():
+def test_reference_simplified_loop_restatement(ref_pins):
     """The simplified loop is inlined in a method full of file I/O (diffusion.py:333-397); its
     restatement is pinned through its building blocks: same schedule, MeanUpsample, and the
     sigma_t = sqrt(1 - abar'^2) quirk documented at diffusion.py:356."""
-    ns = ref_import.load()
-    import importlib
-    import sys
-    sys.path.insert(0, ref_import.REF_ROOT)
-    try:
-        import types
-        for name in ("datasets",):
-            if name not in sys.modules:
-                m = types.ModuleType(name)
-                m.get_dataset = m.data_transform = m.inverse_data_transform = None
-                sys.modules[name] = m
-        ck = types.ModuleType("functions.ckpt_util")
-        ck.get_ckpt_path = ck.download = None
-        sys.modules.setdefault("functions.ckpt_util", ck)
-        D = importlib.import_module("guided_diffusion.diffusion")
-    finally:
-        sys.path.remove(ref_import.REF_ROOT)
-        sys.modules.pop("datasets", None)
-    x = torch.randn(1, 3, 8, 8)
-    assert torch.equal(D.MeanUpsample(x, 4), sampler.mean_upsample(x, 4))
+    x = torch.randn(1, 3, 8, 8, generator=torch.Generator().manual_seed(8))
+    assert torch.equal(torch.from_numpy(ref_pins["simplified_mean_upsample"]), sampler.mean_upsample(x, 4))
     from oracle import operators as O
-    assert torch.equal(D.color2gray(x), O.color2gray(x)) and torch.equal(D.gray2color(x), O.gray2color(x))
-    assert D.get_schedule_jump(100, 10, 3) == schedule.jump_times(100, 10, 3)
+    assert torch.equal(torch.from_numpy(ref_pins["simplified_color2gray"]), O.color2gray(x))
+    assert torch.equal(torch.from_numpy(ref_pins["simplified_gray2color"]), O.gray2color(x))
+    assert ref_pins["simplified_jump_100_10_3"].tolist() == schedule.jump_times(100, 10, 3)
 
 
 @pytest.mark.parametrize("case", cases.SIMPLIFIED_CASES, ids=[c["name"] for c in cases.SIMPLIFIED_CASES])
@@ -206,90 +186,59 @@ def test_oracle_simplified_loop_golden(case, golden_dir):
     assert abs(x.double().abs().sum().item() - st[2]) < 2e-5 * st[2]
 
 
-@needs_ref
-def test_schedules_match_reference_on_random_parameters():
+def test_schedules_match_reference_on_random_parameters(ref_pins):
     """The DDNM time-travel schedule (functions/svd_ddnm.py:167-206) on 3000 random (T, length, repeat) triples:
     reference == oracle == engine, including the parameter sets the reference rejects."""
-    import random
     from ddnm_amd.functions.svd_ddnm import get_schedule_jump
-    ns = ref_import.load()
-    rnd = random.Random(5)
-    for _ in range(3000):
-        T, tl, tr = rnd.randint(1, 150), rnd.randint(1, 15), rnd.randint(1, 5)
+    params, digests = ref_pins["jump_params"], ref_pins["jump_digests"]
+    assert len(params) == len(digests) == 3000
+    for (T, tl, tr), want in zip(params.tolist(), digests.tolist()):
         outs = []
-        for fn in (ns.svd_ddnm.get_schedule_jump, schedule.jump_times, get_schedule_jump):
+        for fn in (schedule.jump_times, get_schedule_jump):
             try:
                 outs.append(fn(T, tl, tr))
             except AssertionError:
                 outs.append("assert")
-        assert outs[0] == outs[1] == outs[2], (T, tl, tr)
+        assert _digest(outs[0]) == want and outs[0] == outs[1], (T, tl, tr)
 
 
-def test_hq_host_logic_matches_reference_on_random_parameters():
+def test_hq_host_logic_matches_reference_on_random_parameters(ref_pins):
     """hq_demo's scheduler and respacing (hq_demo/guided_diffusion/{scheduler,respace}.py) on random parameters:
-    reference == oracle == engine (run in a subprocess: hq_demo's `guided_diffusion` package shadows the main one)."""
-    import os
-    import subprocess
-    import sys
-    if not ref_import.available():
-        pytest.skip("/root/reference not present on this box")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = r'''
-import sys, types, random, importlib
-sys.modules.setdefault("blobfile", types.ModuleType("blobfile"))
-sys.path.insert(0, HQ)
-sch = importlib.import_module("guided_diffusion.scheduler")
-rsp = importlib.import_module("guided_diffusion.respace")
-sys.path.pop(0)
-sys.path.insert(0, ROOT)
-from oracle import hq_demo as H
-from ddnm_amd.hq_demo import get_schedule_jump, space_timesteps
-rnd = random.Random(7)
-for _ in range(2000):
-    kw = dict(t_T=rnd.randint(2, 120), n_sample=rnd.randint(1, 3), jump_length=rnd.randint(1, 15),
-              jump_n_sample=rnd.randint(1, 5), jump2_length=rnd.randint(1, 6), jump2_n_sample=rnd.randint(1, 3),
-              jump3_length=rnd.randint(1, 4), jump3_n_sample=rnd.randint(1, 3),
-              start_resampling=rnd.choice([100000000, 50, 20]))
-    outs = []
-    for fn in (sch.get_schedule_jump, H.schedule_jump, get_schedule_jump):
-        try:
-            outs.append(fn(**kw))
-        except AssertionError:
-            outs.append("assert")
-    assert outs[0] == outs[1] == outs[2], kw
-for _ in range(5000):
-    steps = rnd.randint(2, 1200)
-    spec = ",".join(str(rnd.randint(1, 60)) for _ in range(rnd.randint(1, 4)))
-    outs = []
-    for fn in (rsp.space_timesteps, H.space_timesteps, space_timesteps):
-        try:
-            outs.append(sorted(fn(steps, spec)))
-        except ValueError:
-            outs.append("ValueError")
-    assert outs[0] == outs[1] == outs[2], (steps, spec)
-print("OK")
-'''.replace("HQ", repr(os.path.join(ref_import.REF_ROOT, "hq_demo"))).replace("ROOT", repr(root))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
+    reference == oracle == engine."""
+    from oracle import hq_demo as H
+    from ddnm_amd.hq_demo import get_schedule_jump, space_timesteps
+    keys = ("t_T", "n_sample", "jump_length", "jump_n_sample", "jump2_length", "jump2_n_sample", "jump3_length",
+            "jump3_n_sample", "start_resampling")
+    assert len(ref_pins["hq_jump_params"]) == len(ref_pins["hq_jump_digests"]) == 2000
+    for p, want in zip(ref_pins["hq_jump_params"].tolist(), ref_pins["hq_jump_digests"].tolist()):
+        kw = dict(zip(keys, p))
+        outs = []
+        for fn in (H.schedule_jump, get_schedule_jump):
+            try:
+                outs.append(fn(**kw))
+            except AssertionError:
+                outs.append("assert")
+        assert _digest(outs[0]) == want and outs[0] == outs[1], kw
+    assert len(ref_pins["hq_space_steps"]) == len(ref_pins["hq_space_specs"]) == len(ref_pins["hq_space_digests"]) == 5000
+    for steps, spec, want in zip(ref_pins["hq_space_steps"].tolist(), ref_pins["hq_space_specs"].tolist(),
+                                 ref_pins["hq_space_digests"].tolist()):
+        outs = []
+        for fn in (H.space_timesteps, space_timesteps):
+            try:
+                outs.append(sorted(fn(steps, spec)))
+            except ValueError:
+                outs.append("ValueError")
+        assert _digest(outs[0]) == want and outs[0] == outs[1], (steps, spec)
 
 
-@needs_ref
 @pytest.mark.parametrize("factor", [2, 4, 8, 16])
-def test_bicubic_and_gaussian_kernels_match_reference_source(factor):
+def test_bicubic_and_gaussian_kernels_match_reference_source(factor, ref_pins):
     """The operator factory of the reference is inlined in `svd_based_ddnm_plus` (diffusion.py:451-523) and cannot be
-    imported; its kernel-building statements are executed verbatim from the source file here and compared with the
-    oracle's and the engine's builders (bit-exact)."""
-    import os
-    import textwrap
+    imported; the kernel its kernel-building statements produce (executed verbatim from the source file by
+    tests/golden/make_golden_ref_pins.py) is compared with the oracle's and the engine's builders (bit-exact)."""
     from oracle import operators as O
     from ddnm_amd.functions import svd_operators as E
-    src = open(os.path.join(ref_import.REF_ROOT, "guided_diffusion", "diffusion.py")).read().split("\n")
-    a = next(i for i, l in enumerate(src) if "def bicubic_kernel(x, a=-0.5):" in l)
-    b = next(i for i, l in enumerate(src) if "kernel = torch.from_numpy(k).float()" in l)
-    block = textwrap.dedent("\n".join(src[a:b + 1])).replace(".to(self.device)", "")
-    env = {"np": np, "torch": torch, "factor": factor}
-    exec(block, env)                                                       # noqa: S102 (reference source, test only)
-    ref = env["kernel"] / env["kernel"].sum()                              # the argument SRConv receives (:498)
+    ref = torch.from_numpy(ref_pins[f"bicubic_kernel_{factor}"])           # the argument SRConv receives (:498)
     assert torch.equal(O.bicubic_kernel(factor), ref)
     assert torch.equal(E.bicubic_kernel(factor), ref)
     if factor == 2:
@@ -300,60 +249,40 @@ def test_bicubic_and_gaussian_kernels_match_reference_source(factor):
             assert torch.equal(E.gaussian_taps(sigma, radius), want)
 
 
-@needs_ref
-def test_beta_schedules_and_alpha_table_match_reference():
+def test_beta_schedules_and_alpha_table_match_reference(ref_pins):
     """`get_beta_schedule` for every schedule name (diffusion.py:46-76) and `compute_alpha` for every t in
     [-1, 999] (svd_ddnm.py:10-13): reference == engine, bit for bit."""
-    import importlib
-    import sys
-    import types
     from ddnm_amd.functions.svd_ddnm import _AlphaTable, compute_alpha
     from ddnm_amd.guided_diffusion.diffusion import get_beta_schedule
-    ns = ref_import.load()
-    sys.path.insert(0, ref_import.REF_ROOT)
-    try:
-        sys.modules.setdefault("datasets", types.ModuleType("datasets"))
-        for attr in ("get_dataset", "data_transform", "inverse_data_transform"):
-            setattr(sys.modules["datasets"], attr, None)
-        ck = types.ModuleType("functions.ckpt_util")
-        ck.get_ckpt_path = ck.download = None
-        sys.modules.setdefault("functions.ckpt_util", ck)
-        D = importlib.import_module("guided_diffusion.diffusion")
-    finally:
-        sys.path.remove(ref_import.REF_ROOT)
-        sys.modules.pop("datasets", None)
     for name in ("quad", "linear", "const", "jsd", "sigmoid"):
         for n in (10, 1000):
             kw = dict(beta_start=1e-4, beta_end=0.02, num_diffusion_timesteps=n)
-            assert np.array_equal(D.get_beta_schedule(name, **kw), get_beta_schedule(name, **kw)), name
+            assert np.array_equal(ref_pins[f"beta_schedule_{name}_{n}"], get_beta_schedule(name, **kw)), name
     betas = torch.from_numpy(get_beta_schedule("linear", beta_start=1e-4, beta_end=0.02,
                                                num_diffusion_timesteps=1000)).float()
     table = _AlphaTable(betas)
+    alphas = torch.from_numpy(ref_pins["compute_alpha_m1_to_999"])           # the reference's compute_alpha, t = -1 .. 999
+    assert alphas.shape[0] == 1001
     for t in range(-1, 1000):
         tt = torch.full((2,), t, dtype=torch.long)
-        want = ns.svd_ddnm.compute_alpha(betas, tt)
+        want = alphas[t + 1]
         assert torch.equal(compute_alpha(betas, tt), want)
         assert float(table(t)) == float(want[0, 0, 0, 0])
 
 
-@needs_ref
 @pytest.mark.parametrize("seed", [0, 1, 2])
-def test_inpainting_real_constructor_small(seed):
+def test_inpainting_real_constructor_small(seed, ref_pins):
     """The REAL `Inpainting.__init__` (its O(n*m) kept-index loop, svd_operators.py:324-333) at 16x16 -- the golden
     generator bypasses it at full size -- against the oracle operator: A, A_pinv and the index order."""
     from oracle import operators as O
-    ns = ref_import.load()
     g = torch.Generator().manual_seed(seed)
     d = 16
     mask = (torch.rand(d, d, generator=g) > 0.3).long()
-    r = torch.nonzero(mask.reshape(-1) == 0).long().reshape(-1) * 3                    # diffusion.py:465-470
-    missing = torch.cat([r, r + 1, r + 2], dim=0)
-    ref = ns.svd_operators.Inpainting(3, d, missing, "cpu")
     orc = O.Inpainting(3, d, O.Inpainting.missing_from_mask(mask))
     x = torch.randn(2, 3, d, d, generator=g)
-    y = ref.A(x)
+    y = torch.from_numpy(ref_pins[f"inpainting_ctor_{seed}_y"])              # the reference's Inpainting(...).A(x)
     assert torch.equal(orc.A(x), y)
-    assert torch.equal(orc.A_pinv(y).reshape(2, -1), ref.A_pinv(y.clone()).reshape(2, -1))
+    assert torch.equal(orc.A_pinv(y).reshape(2, -1), torch.from_numpy(ref_pins[f"inpainting_ctor_{seed}_pinv"]))
 
 
 def test_oracle_superresolution_ratio16_golden(golden_dir):

@@ -80,4 +80,4 @@ if d.get("source_digest") == st.get("source_digest"):
     json.dump(d, open("gpurun_out/${R}_pmc_dominant_kernel.json", "w"), indent=1)
 PY
 cp gpurun_out/${R}_pmc_dominant_kernel.json gpurun_out/${R}_pmc_dominant_kernel.md gpurun_out/${R}_adm_pmc_conv16.json gpurun_out/${R}_adm_pmc_conv16.md profiles/
-timeout 1200 python bench.py --steps ${BENCH_STEPS:-5} --warmup 2 > gpurun_out/${R}_bench_line.json 2> gpurun_out/bench.log; cat gpurun_out/${R}_bench_line.json
+timeout 1200 python bench.py --full --steps ${BENCH_STEPS:-5} --warmup 2 > profiles/${R}_bench_line.json; cat profiles/${R}_bench_line.json
