@@ -201,6 +201,17 @@ PROTOTYPES = {
     "ddnm_attn_fused_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_void_p]),
     "ddnm_attn_fused_supported": (c_int32, [c_int32, c_int32]),
     "ddnm_randn_philox_f32": (c_int32, [c_void_p, c_int32, c_int64, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p]),
+    "ddnm_randn_philox_keyed_f32": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_uint32, c_void_p]),
+    "ddnm_step_combine_keyed_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                              c_int32, c_int64, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_sr_avgpool_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_int32, c_int32, c_int32, c_int32, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_color_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_int32, POINTER(c_float), POINTER(StepScalars), c_void_p]),
+    "ddnm_step_inpaint_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                              c_void_p, c_void_p, c_int32, c_int32, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_denoise_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int32, c_int64, POINTER(StepScalars), c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ddnm_op_avgpool_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_op_upsample_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

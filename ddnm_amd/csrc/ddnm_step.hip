@@ -38,6 +38,31 @@ __device__ __forceinline__ f32x4 nz4(const NoiseSrc& n, int64_t off) {
     return philox_normal4(n.key, (unsigned)(r >> 2), n.iter, n.img_base + (unsigned)b);
 }
 
+// Per-image keys (the *_keyed_f32 entry points): row b of `keys` = {key_lo, key_hi, image counter, 0}, so that images of
+// different loader batches (different seeds) share a launch.  Rows {seed_lo, seed_hi, img_base + b, 0} give NoiseSrc's
+// draw.  The kernels below are templates on the source; the NoiseSrc instantiations are the unkeyed entry points.
+struct KeyedNoiseSrc {
+    const uint4* keys;
+    unsigned iter;
+    int64_t chw;
+};
+static inline KeyedNoiseSrc keyed_src(const uint32_t* keys, const ddnm_step_scalars* s, int64_t chw) {
+    return KeyedNoiseSrc{reinterpret_cast<const uint4*>(keys), s->rng_iter, chw};
+}
+static inline bool keys_ok(const uint32_t* keys) { return keys != nullptr && (reinterpret_cast<uintptr_t>(keys) & 15) == 0; }
+// `bind(src, b)` at the top of a kernel's loop body: the keyed source loads image b's key row there, ahead of the
+// operand loads (its latency hides behind theirs), and draws by offset within the image; NoiseSrc is returned as is.
+struct KeyedRow {
+    uint4 k;
+    unsigned iter;
+    int64_t base;    // b * chw
+};
+__device__ __forceinline__ const NoiseSrc& bind(const NoiseSrc& n, int64_t) { return n; }
+__device__ __forceinline__ KeyedRow bind(const KeyedNoiseSrc& n, int64_t b) { return KeyedRow{n.keys[b], n.iter, b * n.chw}; }
+__device__ __forceinline__ f32x4 nz4(const KeyedRow& n, int64_t off) {
+    return philox_normal4(PhiloxKey{n.k.x, n.k.y}, (unsigned)((off - n.base) >> 2), n.iter, n.k.z);
+}
+
 __device__ __forceinline__ f32x4 x0_of(f32x4 xt, f32x4 et, const ddnm_step_scalars& s) {
     return (xt - et * s.sqrt_1m_at) / s.sqrt_at;
 }
@@ -65,18 +90,20 @@ extern "C" int ddnm_step_x0_f32(const float* xt, const float* et, int64_t et_bst
     return 0;
 }
 
+template <class NZ>
 __global__ __launch_bounds__(256) void step_combine_kernel(const float* __restrict__ x0, const float* __restrict__ proj,
                                                            const float* __restrict__ apy,
-                                                           NoiseSrc noise,
+                                                           NZ noise,
                                                            const float* __restrict__ et, int64_t et_bstride,
                                                            float* __restrict__ xt_next, int64_t chw4, int64_t total4,
                                                            ddnm_step_scalars s) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / chw4, r = i - b * chw4;
+        const auto nz = bind(noise, b);
         f32x4 p = ld4(proj + i * 4);
         if (apy) p = p - ld4(apy + i * 4);
         const f32x4 x0h = ld4(x0 + i * 4) - p * s.lambda;
-        st4(xt_next + i * 4, update_of(x0h, nz4(noise, i * 4), ld4(et + b * et_bstride + r * 4), s));
+        st4(xt_next + i * 4, update_of(x0h, nz4(nz, i * 4), ld4(et + b * et_bstride + r * 4), s));
     }
 }
 
@@ -86,15 +113,16 @@ extern "C" int ddnm_step_combine_f32(const float* x0, const float* proj, const f
     if (!x0 || !proj || !et || !xt_next || !s || B <= 0 || chw <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(step_combine_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x0, proj, apy, noise_src(noise, s, chw),
+    DDNM_LAUNCH(step_combine_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x0, proj, apy, noise_src(noise, s, chw),
                        et, et_bstride, xt_next, chw / 4, total4, *s);
     return 0;
 }
 
 // ---------------------------------------------------------------- fused: SR by average pooling, r = 4
 // one thread per 4x4 patch: 4 rows x float4.
+template <class NZ>
 __global__ __launch_bounds__(256) void step_sr4_kernel(const float* __restrict__ xt, const float* __restrict__ et,
-                                                       int64_t et_bstride, NoiseSrc noise,
+                                                       int64_t et_bstride, NZ noise,
                                                        const float* __restrict__ y, float* __restrict__ x0o,
                                                        float* __restrict__ xn, int H, int W, int64_t total,
                                                        ddnm_step_scalars s) {
@@ -102,6 +130,7 @@ __global__ __launch_bounds__(256) void step_sr4_kernel(const float* __restrict__
     const int64_t per_img = (int64_t)3 * Hy * Wy;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / per_img;
+        const auto nz = bind(noise, b);
         int64_t r = i - b * per_img;
         const int c = (int)(r / ((int64_t)Hy * Wy));
         r -= (int64_t)c * Hy * Wy;
@@ -122,7 +151,7 @@ __global__ __launch_bounds__(256) void step_sr4_kernel(const float* __restrict__
         for (int j = 0; j < 4; ++j) {
             if (x0o) st4(x0o + off + (int64_t)j * W, x0[j]);
             const f32x4 x0h = x0[j] - corr;
-            st4(xn + off + (int64_t)j * W, update_of(x0h, nz4(noise, off + (int64_t)j * W), e[j], s));
+            st4(xn + off + (int64_t)j * W, update_of(x0h, nz4(nz, off + (int64_t)j * W), e[j], s));
         }
     }
 }
@@ -133,7 +162,7 @@ extern "C" int ddnm_step_sr_avgpool_f32(const float* xt, const float* et, int64_
     if (!xt || !et || !y || !xt_next || !s || B <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if (r != 4 || (H & 3) || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total = (int64_t)B * 3 * (H / 4) * (W / 4);
-    DDNM_LAUNCH(step_sr4_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+    DDNM_LAUNCH(step_sr4_kernel<NoiseSrc>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
                 noise_src(noise, s, (int64_t)3 * H * W),
                        y, x0, xt_next, H, W, total, *s);
     return 0;
@@ -152,13 +181,15 @@ static ColorW color_weights(const float* w3_host) {
     return c;
 }
 
+template <class NZ>
 __global__ __launch_bounds__(256) void step_color_kernel(const float* __restrict__ xt, const float* __restrict__ et,
-                                                         int64_t et_bstride, NoiseSrc noise,
+                                                         int64_t et_bstride, NZ noise,
                                                          const float* __restrict__ y, float* __restrict__ x0o,
                                                          float* __restrict__ xn, int64_t hw4, int64_t total4,
                                                          ddnm_step_scalars s, ColorW cw) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / hw4, p = i - b * hw4;
+        const auto nz = bind(noise, b);
         const int64_t base = (b * 3 * hw4 + p) * 4, ebase = b * et_bstride + p * 4;
         f32x4 e[3], x0[3];
 #pragma unroll
@@ -172,7 +203,7 @@ __global__ __launch_bounds__(256) void step_color_kernel(const float* __restrict
         for (int c = 0; c < 3; ++c) {
             if (x0o) st4(x0o + base + c * hw4 * 4, x0[c]);
             const f32x4 x0h = x0[c] - resid * cw.wp[c];
-            st4(xn + base + c * hw4 * 4, update_of(x0h, nz4(noise, base + c * hw4 * 4), e[c], s));
+            st4(xn + base + c * hw4 * 4, update_of(x0h, nz4(nz, base + c * hw4 * 4), e[c], s));
         }
     }
 }
@@ -183,20 +214,22 @@ extern "C" int ddnm_step_color_f32(const float* xt, const float* et, int64_t et_
     if (!xt || !et || !y || !xt_next || !s || B <= 0 || HW <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_color_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+    DDNM_LAUNCH(step_color_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
                        noise_src(noise, s, (int64_t)3 * HW), y, x0, xt_next, (int64_t)HW / 4, total4, *s, color_weights(w3_host));
     return 0;
 }
 
 // ---------------------------------------------------------------- fused: inpainting (mask as rank table)
+template <class NZ>
 __global__ __launch_bounds__(256) void step_inpaint_kernel(const float* __restrict__ xt, const float* __restrict__ et,
-                                                           int64_t et_bstride, NoiseSrc noise,
+                                                           int64_t et_bstride, NZ noise,
                                                            const float* __restrict__ y, const int* __restrict__ rank,
                                                            int n_kept, float* __restrict__ x0o,
                                                            float* __restrict__ xn, int64_t hw4, int64_t total4,
                                                            ddnm_step_scalars s) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / hw4, p = i - b * hw4;
+        const auto nz = bind(noise, b);
         const int64_t base = (b * 3 * hw4 + p) * 4, ebase = b * et_bstride + p * 4;
         const int4 rk = *reinterpret_cast<const int4*>(rank + p * 4);
         const int rks[4] = {rk.x, rk.y, rk.z, rk.w};
@@ -210,7 +243,7 @@ __global__ __launch_bounds__(256) void step_inpaint_kernel(const float* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (rks[j] >= 0) x0h[j] = x0[j] - (x0[j] - yb[(int64_t)rks[j] * 3 + c]) * s.lambda;
-            st4(xn + base + c * hw4 * 4, update_of(x0h, nz4(noise, base + c * hw4 * 4), e, s));
+            st4(xn + base + c * hw4 * 4, update_of(x0h, nz4(nz, base + c * hw4 * 4), e, s));
         }
     }
 }
@@ -221,24 +254,26 @@ extern "C" int ddnm_step_inpaint_f32(const float* xt, const float* et, int64_t e
     if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_inpaint_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+    DDNM_LAUNCH(step_inpaint_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
                        noise_src(noise, s, (int64_t)3 * HW), y, rank, n_kept, x0, xt_next, (int64_t)HW / 4, total4, *s);
     return 0;
 }
 
 // ---------------------------------------------------------------- fused: denoising (A = I)
+template <class NZ>
 __global__ __launch_bounds__(256) void step_denoise_kernel(const float* __restrict__ xt, const float* __restrict__ et,
-                                                           int64_t et_bstride, NoiseSrc noise,
+                                                           int64_t et_bstride, NZ noise,
                                                            const float* __restrict__ y, float* __restrict__ x0o,
                                                            float* __restrict__ xn, int64_t chw4, int64_t total4,
                                                            ddnm_step_scalars s) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / chw4, r = i - b * chw4;
+        const auto nz = bind(noise, b);
         const f32x4 e = ld4(et + b * et_bstride + r * 4);
         const f32x4 x0 = x0_of(ld4(xt + i * 4), e, s);
         if (x0o) st4(x0o + i * 4, x0);
         const f32x4 x0h = x0 - (x0 - ld4(y + i * 4)) * s.lambda;
-        st4(xn + i * 4, update_of(x0h, nz4(noise, i * 4), e, s));
+        st4(xn + i * 4, update_of(x0h, nz4(nz, i * 4), e, s));
     }
 }
 
@@ -248,8 +283,64 @@ extern "C" int ddnm_step_denoise_f32(const float* xt, const float* et, int64_t e
     if (!xt || !et || !y || !xt_next || !s || B <= 0 || chw <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(step_denoise_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+    DDNM_LAUNCH(step_denoise_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
                        noise_src(noise, s, chw), y, x0, xt_next, chw / 4, total4, *s);
+    return 0;
+}
+
+// ---------------------------------------------------------------- keyed entry points: same kernels, per-image keys
+extern "C" int ddnm_step_combine_keyed_f32(const float* x0, const float* proj, const float* apy, const uint32_t* keys,
+                                           const float* et, int64_t et_bstride, float* xt_next, int32_t B, int64_t chw,
+                                           const ddnm_step_scalars* s, void* stream) {
+    if (!x0 || !proj || !et || !xt_next || !s || B <= 0 || chw <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)B * chw / 4;
+    DDNM_LAUNCH(step_combine_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x0, proj, apy,
+                keyed_src(keys, s, chw), et, et_bstride, xt_next, chw / 4, total4, *s);
+    return 0;
+}
+
+extern "C" int ddnm_step_sr_avgpool_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                              const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                              int32_t r, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !xt_next || !s || B <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    if (r != 4 || (H & 3) || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total = (int64_t)B * 3 * (H / 4) * (W / 4);
+    DDNM_LAUNCH(step_sr4_kernel<KeyedNoiseSrc>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                keyed_src(keys, s, (int64_t)3 * H * W), y, x0, xt_next, H, W, total, *s);
+    return 0;
+}
+
+extern "C" int ddnm_step_color_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                         const float* y, float* x0, float* xt_next, int32_t B, int32_t HW,
+                                         const float* w3_host, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !xt_next || !s || B <= 0 || HW <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)B * HW / 4;
+    DDNM_LAUNCH(step_color_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                keyed_src(keys, s, (int64_t)3 * HW), y, x0, xt_next, (int64_t)HW / 4, total4, *s, color_weights(w3_host));
+    return 0;
+}
+
+extern "C" int ddnm_step_inpaint_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                           const float* y, const int32_t* rank, int32_t n_kept, float* x0, float* xt_next,
+                                           int32_t B, int32_t HW, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)B * HW / 4;
+    DDNM_LAUNCH(step_inpaint_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                keyed_src(keys, s, (int64_t)3 * HW), y, rank, n_kept, x0, xt_next, (int64_t)HW / 4, total4, *s);
+    return 0;
+}
+
+extern "C" int ddnm_step_denoise_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                           const float* y, float* x0, float* xt_next, int32_t B, int64_t chw,
+                                           const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !xt_next || !s || B <= 0 || chw <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)B * chw / 4;
+    DDNM_LAUNCH(step_denoise_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                keyed_src(keys, s, chw), y, x0, xt_next, chw / 4, total4, *s);
     return 0;
 }
 
@@ -271,6 +362,36 @@ extern "C" int ddnm_randn_philox_f32(float* out, int32_t B, int64_t chw, uint32_
     const int64_t total4 = (int64_t)B * chw / 4;
     DDNM_LAUNCH(randn_philox_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, out, chw / 4, total4,
                 PhiloxKey{seed_lo, seed_hi}, iter, image_base);
+    return 0;
+}
+
+// keyed draw of any row length n: thread i = (image b, block g of four); rows are 16-byte aligned only when n % 4 == 0,
+// otherwise (and for the last partial block) the values are stored one by one, the partial block's first n % 4 only
+__global__ __launch_bounds__(256) void randn_philox_keyed_kernel(float* __restrict__ out, const uint4* __restrict__ keys,
+                                                                 int64_t n, int64_t n4, int64_t total4, unsigned iter) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / n4, g = i - b * n4;
+        const uint4 k = keys[b];
+        const f32x4 v = philox_normal4(PhiloxKey{k.x, k.y}, (unsigned)g, iter, k.z);
+        float* o = out + b * n + g * 4;
+        if ((n & 3) == 0) {
+            st4(o, v);
+        } else {
+            const int64_t m = n - g * 4;
+            o[0] = v.x;
+            if (m > 1) o[1] = v.y;
+            if (m > 2) o[2] = v.z;
+            if (m > 3) o[3] = v.w;
+        }
+    }
+}
+
+extern "C" int ddnm_randn_philox_keyed_f32(float* out, int32_t B, int64_t n, const uint32_t* keys, uint32_t iter,
+                                           void* stream) {
+    if (!out || B <= 0 || n <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    const int64_t n4 = (n + 3) / 4, total4 = (int64_t)B * n4;
+    DDNM_LAUNCH(randn_philox_keyed_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, out,
+                reinterpret_cast<const uint4*>(keys), n, n4, total4, iter);
     return 0;
 }
 

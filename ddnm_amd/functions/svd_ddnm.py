@@ -25,7 +25,10 @@ INSIDE the step kernels (`ops.PhiloxNoise`: Philox4x32-10 + Box-Muller, counter 
 counter): no noise tensor is written and read back, and no ATen kernel runs in
 the loop.  `noise=ops.PhiloxNoise(seed, image_base)` pins seed and the global
 index of the batch's first image (sharded runs); DDNM_NOISE=torch restores the
-ATen draw from the device generator.
+ATen draw from the device generator.  `noise=ops.KeyedPhiloxNoise(keys, image_ctrs)`
+gives every image its own key and counter: a batch of independently seeded images
+(e.g. several loader batches fused into one call) restored in one run, each image
+drawing exactly what it draws when restored alone.
 
 `return_cpu` (default True) matches the reference, which hands back CPU tensors
 (`xs[-1]`, `x0_preds[-1]` were `.to('cpu')`, svd_ddnm.py:67-68,76-78); the runner, the
@@ -250,6 +253,13 @@ def _noise_source(noise, like):
             return torch.randn_like(like)
         draw.philox = None
         return draw
+    if isinstance(noise, ops.KeyedPhiloxNoise):
+        # per-image keys: the step kernels get the key table (their keyed entry points), x_T / re-noise / DDNM+ eps use
+        # `.philox.tensor`
+        def keyed(k):
+            return noise
+        keyed.philox = noise
+        return keyed
     if noise is None or isinstance(noise, ops.PhiloxNoise):
         ph = _philox_for_call(like) if noise is None else noise
 

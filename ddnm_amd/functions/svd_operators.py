@@ -16,7 +16,9 @@ as one (or a few) hand-written HIP kernels:
 
 Every class also implements `ddnm_step(...)`, the fused x0 / projection / DDIM
 update of one sampler step (functions/svd_ddnm.py:57-65) that `ddnm_diffusion`
-uses when it is handed one of these objects.
+uses when it is handed one of these objects.  Its `noise` is a tensor, None (the
+kernel draws in-kernel from ddnm_step_scalars::rng_*) or an `ops.KeyedPhiloxNoise`
+(per-image keys: the `*_keyed_f32` entry points, ops.step_noise_args).
 
 `Lambda` / `Lambda_noise` (the sigma_y > 0 path of `ddnm_plus_diffusion`) follow the reference's
 per-class definitions, including its quirk of feeding the RAW patch / needle / permuted entries of
@@ -239,9 +241,9 @@ class Denoising(A_functions):
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         B = xt.shape[0]
         ep, es = ops._et_args(et)
-        check(_lib.lib().ddnm_step_denoise_f32(_p(xt), ep, es, _p(noise), _p(y), _p(x0_out), _p(xt_next), B,
-                                               xt.numel() // B, ctypes.byref(s), ops._stream()),
-              "ddnm_step_denoise_f32")
+        fn, nz = ops.step_noise_args("ddnm_step_denoise_f32", noise, xt)
+        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(x0_out), _p(xt_next), B, xt.numel() // B,
+                                      ctypes.byref(s), ops._stream()), fn)
 
 
 class SuperResolution(A_functions):
@@ -333,9 +335,9 @@ class SuperResolution(A_functions):
             return super().ddnm_step(xt, et, noise, y, s, x0_out, xt_next)
         B = xt.shape[0]
         ep, es = ops._et_args(et)
-        check(_lib.lib().ddnm_step_sr_avgpool_f32(_p(xt), ep, es, _p(noise), _p(y), _p(x0_out), _p(xt_next), B,
-                                                  self.img_dim, self.img_dim, self.ratio, ctypes.byref(s),
-                                                  ops._stream()), "ddnm_step_sr_avgpool_f32")
+        fn, nz = ops.step_noise_args("ddnm_step_sr_avgpool_f32", noise, xt)
+        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(x0_out), _p(xt_next), B, self.img_dim, self.img_dim,
+                                      self.ratio, ctypes.byref(s), ops._stream()), fn)
 
 
 class Colorization(A_functions):
@@ -405,9 +407,9 @@ class Colorization(A_functions):
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         B = xt.shape[0]
         ep, es = ops._et_args(et)
-        check(_lib.lib().ddnm_step_color_f32(_p(xt), ep, es, _p(noise), _p(y), _p(x0_out), _p(xt_next), B,
-                                             self.img_dim ** 2, self._w, ctypes.byref(s), ops._stream()),
-              "ddnm_step_color_f32")
+        fn, nz = ops.step_noise_args("ddnm_step_color_f32", noise, xt)
+        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(x0_out), _p(xt_next), B, self.img_dim ** 2, self._w,
+                                      ctypes.byref(s), ops._stream()), fn)
 
 
 class Inpainting(A_functions):
@@ -489,9 +491,9 @@ class Inpainting(A_functions):
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         B = xt.shape[0]
         ep, es = ops._et_args(et)
-        check(_lib.lib().ddnm_step_inpaint_f32(_p(xt), ep, es, _p(noise), _p(y), _p(self.rank), self.n_kept,
-                                               _p(x0_out), _p(xt_next), B, self.img_dim ** 2, ctypes.byref(s),
-                                               ops._stream()), "ddnm_step_inpaint_f32")
+        fn, nz = ops.step_noise_args("ddnm_step_inpaint_f32", noise, xt)
+        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(self.rank), self.n_kept, _p(x0_out), _p(xt_next), B,
+                                      self.img_dim ** 2, ctypes.byref(s), ops._stream()), fn)
 
 
 class WalshHadamardCS(A_functions):

@@ -13,7 +13,10 @@ Deliberate differences at the boundary (not in the results):
   * multi-GPU is one process per GPU (ddnm_amd.dist), not `torch.nn.DataParallel` (:140,164): every rank sees the
     same batches, restores the images [lo, hi) of each batch (its slice of x_T and of the per-step noise, both drawn
     for the WHOLE batch from a per-batch generator so the result does not depend on the number of ranks), and the
-    restored shards meet in ONE RCCL all_gather per batch; rank 0 writes the PNGs and reports the PSNR.
+    restored shards meet in ONE RCCL all_gather per batch; rank 0 writes the PNGs and reports the PSNR;
+  * DDNM_FUSE_BATCHES=K (default 1) restores up to K consecutive loader batches of a rank in one sampler call, each image
+    with the noise it gets alone (per-image Philox keys, ops.KeyedPhiloxNoise): the shipped configs' batch of one image
+    leaves most of the chip idle.  Files, PSNR lines and totals are those of the unfused run.
 """
 import os
 import random
@@ -219,6 +222,55 @@ class BatchNoise:
         return self.draw()[self.lo:self.hi].contiguous()
 
 
+def measurement_noise(key, like):
+    """N(0, I) of `--add_noise` for y viewed as [b, n] (Philox key `key`, image counter = index in the batch): the
+    unkeyed draw when n % 4 == 0, else the keyed one, which takes any n (inpainting's y has 3 * n_kept entries) and gives
+    the same values on the whole blocks of four."""
+    src = ops.PhiloxNoise(key, 0)
+    if like.shape[1] % 4 == 0:
+        return src.tensor(0, like)
+    return ops.KeyedPhiloxNoise.from_sources([(src, i) for i in range(like.shape[0])]).tensor(0, like)
+
+
+class FusedTape:
+    """Noise tape of a fused sampler call: `tape[k]` = the concatenation of each loader batch's own draw k (BatchNoise
+    tapes, or per-image lists of the simplified path), so every part keeps the sequence it has when restored alone."""
+
+    def __init__(self, parts):
+        self.parts = list(parts)
+
+    def __getitem__(self, k):
+        return torch.cat([p[k] for p in self.parts], 0)
+
+
+# DDNM_FUSE_BATCHES=K: restore up to K consecutive loader batches of this rank in ONE sampler call (default 1 = off)
+def fuse_batches():
+    k = int(os.environ.get("DDNM_FUSE_BATCHES", "1"))
+    if k < 1:
+        raise ValueError(f"DDNM_FUSE_BATCHES must be >= 1, got {k}")
+    return k
+
+
+# the simplified path pre-draws x_T and every loop iteration's ATen noise of a fused group (to replay the unfused draw
+# order): (n_iter + 1) * K * C * S^2 * 4 bytes, kept under this bound by capping K (celeba / ADM at 256^2, T = 100:
+# 79 MB per image, K <= 27)
+SIMPLIFIED_TAPE_BYTES = 2 << 30
+
+
+def fuse_groups(n_items, batch_size, rank, world, k):
+    """Loader batches restored by `rank`, grouped into sampler calls: a list of groups, each a list of
+    (batch index, index of its first image in the loader order, batch size).  Fusing needs whole loader batches per rank
+    -- one rank, or deal mode (batch_size < world: batch bi belongs to rank bi % world) -- and takes up to `k`
+    consecutive owned batches per group (the last group may be shorter).  Split mode (batch_size >= world > 1: every
+    rank restores a slice of every batch) and k == 1 give one batch per group."""
+    sizes = [min(batch_size, n_items - lo) for lo in range(0, n_items, batch_size)]
+    starts = [i * batch_size for i in range(len(sizes))]
+    deal = world > 1 and batch_size < world
+    owned = [(bi, starts[bi], b) for bi, b in enumerate(sizes) if not deal or bi % world == rank]
+    step = k if (world == 1 or deal) else 1
+    return [owned[i:i + step] for i in range(0, len(owned), step)]
+
+
 class Diffusion(object):
     def __init__(self, args, config, device=None):
         self.args, self.config = args, config
@@ -383,6 +435,37 @@ class Diffusion(object):
         # function of (seed, batch index, image index in the batch) only.
         deal = world > 1 and config.sampling.batch_size < world
         philox = os.environ.get("DDNM_NOISE") != "torch"      # in-kernel Philox draws (default) | ATen tape (BatchNoise)
+        # DDNM_FUSE_BATCHES=K: up to K consecutive loader batches of this rank restored in ONE sampler call (per-image
+        # noise keys: each image draws what it draws alone); needs whole batches per rank
+        K = fuse_batches()
+        fuse = K > 1 and (world == 1 or deal)
+        if K > 1 and not fuse:
+            print(f"[ddnm_amd] DDNM_FUSE_BATCHES={K} ignored: loader batches of {config.sampling.batch_size} images are "
+                  f"split over {world} ranks")
+        group_ends = {g[-1][0] for g in fuse_groups(len(loader.dataset), config.sampling.batch_size, rank, world, K)} \
+            if fuse else set()
+        pending = []
+
+        def finish(x_all, x_orig, idx0):
+            nonlocal psnr_sum, n_done
+            b = x_orig.shape[0]
+            img, psnr = ops.finalize_psnr(x_all.contiguous(), x_orig)
+            for j in range(b):
+                save_image(img[j], os.path.join(args.image_folder, f"{idx0 + j}_{0}.png"))
+            psnr_sum += float(psnr.sum())
+            n_done += b
+            print("PSNR: %.2f" % (psnr_sum / n_done))
+
+        def restore(x, y_loc, classes, noise):
+            with torch.no_grad():
+                if sigma_y == 0.0:       # noise-free case, DDNM (diffusion.py:587-588)
+                    xs, _ = ddnm_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, cls_fn=cls_fn,
+                                           classes=classes, config=config, noise=noise, return_cpu=False)
+                else:                    # noisy case, DDNM+ (:589-590)
+                    xs, _ = ddnm_plus_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, sigma_y, cls_fn=cls_fn,
+                                                classes=classes, config=config, noise=noise, return_cpu=False)
+            return xs[0]
+
         for bi, (x_orig, classes) in enumerate(loader):
             b = x_orig.shape[0]
             if deal and bi % world != rank:
@@ -403,7 +486,7 @@ class Diffusion(object):
             y = A_funcs.A(x_orig)                # the whole batch: operators are cheap, and the writer needs A^+ y of all
             if args.add_noise:
                 if philox:
-                    y = y + ops.PhiloxNoise(_mix64(args.seed, bi) ^ 0x5DEECE66D, 0).tensor(0, y.reshape(b, -1)).reshape(y.shape) * sigma_y
+                    y = y + measurement_noise(_mix64(args.seed, bi) ^ 0x5DEECE66D, y.reshape(b, -1)).reshape(y.shape) * sigma_y
                 else:
                     y = y + noise.draw(tuple(y.shape)) * sigma_y
             if writer:
@@ -419,26 +502,31 @@ class Diffusion(object):
                                os.path.join(args.image_folder, f"Apy/Apy_{idx_so_far + i}.png"))
                     save_image(ops.finalize_psnr(x_orig[i:i + 1])[0][0],
                                os.path.join(args.image_folder, f"Apy/orig_{idx_so_far + i}.png"))
+            if fuse:
+                # whole batches (lo, hi = 0, b): held until the last batch of the group, restored together
+                pending.append((x, y.reshape(b, -1).contiguous(), classes, noise, x_orig, idx_so_far))
+                if bi in group_ends:
+                    if philox:
+                        fnoise = ops.KeyedPhiloxNoise.from_sources([(p[3], j) for p in pending for j in range(p[4].shape[0])])
+                    else:
+                        fnoise = FusedTape([p[3] for p in pending])
+                    x_fused = restore(torch.cat([p[0] for p in pending], 0), torch.cat([p[1] for p in pending], 0),
+                                      torch.cat([p[2] for p in pending], 0), fnoise)
+                    off = 0
+                    for p in pending:                # one PSNR line per loader batch, in loader order
+                        nb = p[4].shape[0]
+                        finish(x_fused[off:off + nb], p[4], p[5])
+                        off += nb
+                    pending = []
+                idx_so_far += b
+                continue
             if hi > lo:
-                y_loc = y.reshape(b, -1)[lo:hi].contiguous()
-                with torch.no_grad():
-                    if sigma_y == 0.0:       # noise-free case, DDNM (diffusion.py:587-588)
-                        xs, _ = ddnm_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, cls_fn=cls_fn,
-                                               classes=classes, config=config, noise=noise, return_cpu=False)
-                    else:                    # noisy case, DDNM+ (:589-590)
-                        xs, _ = ddnm_plus_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, sigma_y, cls_fn=cls_fn,
-                                                    classes=classes, config=config, noise=noise, return_cpu=False)
-                x_loc = xs[0]
+                x_loc = restore(x, y.reshape(b, -1)[lo:hi].contiguous(), classes, noise)
             else:
                 x_loc = x                    # empty shard (fewer images than ranks): takes part in the gather only
             x_all = x_loc if deal else ddist.gather_images(x_loc, n_total=b)      # the path's single collective (one per batch)
             if writer:
-                img, psnr = ops.finalize_psnr(x_all.contiguous(), x_orig)
-                for j in range(b):
-                    save_image(img[j], os.path.join(args.image_folder, f"{idx_so_far + j}_{0}.png"))
-                psnr_sum += float(psnr.sum())
-                n_done += b
-                print("PSNR: %.2f" % (psnr_sum / n_done))
+                finish(x_all, x_orig, idx_so_far)
             idx_so_far += b
         if deal:
             psnr_sum, n_done = ddist.reduce_sum(psnr_sum, self.device), int(ddist.reduce_sum(n_done, self.device))
@@ -479,6 +567,24 @@ class Diffusion(object):
         idx_so_far = args.subset_start
         psnr_sum, n_done = 0.0, 0
         os.makedirs(os.path.join(args.image_folder, "Apy"), exist_ok=True)
+        # DDNM_FUSE_BATCHES=K: up to K of this rank's images in one loop.  The loop's noise is ATen's (torch.randn), so the
+        # unfused draw order -- per image: x_T, then one draw per loop iteration -- is replayed into a tape up front
+        tt = config.time_travel
+        n_iter = len(get_schedule_jump(tt.T_sampling, tt.travel_length, tt.travel_repeat)) - 1
+        per_image = (n_iter + 1) * config.data.channels * config.data.image_size ** 2 * 4
+        K = min(fuse_batches(), max(1, SIMPLIFIED_TAPE_BYTES // per_image))
+        group_ends = {g[-1][0] for g in fuse_groups(len(loader.dataset), 1, rank, world, K)} if K > 1 else set()
+        pending = []
+
+        def finish(x, x_orig, idx0):
+            nonlocal psnr_sum, n_done
+            img, psnr = ops.finalize_psnr(x, x_orig)
+            # the reference names the file with the stale loop variable j = -1 (:402); reproduced
+            save_image(img[0], os.path.join(args.image_folder, f"{idx0 + (-1)}_{0}.png"))
+            psnr_sum += float(psnr[0])
+            n_done += x_orig.shape[0]
+            print("PSNR: %.2f" % (psnr_sum / n_done))
+
         for bi, (x_orig, classes) in enumerate(loader):
             if config.sampling.batch_size != 1:
                 raise ValueError("please change the config file to set batch size as 1")
@@ -492,14 +598,20 @@ class Diffusion(object):
             save_image(ops.finalize_psnr(x_orig)[0][0], os.path.join(args.image_folder, f"Apy/orig_{idx_so_far}.png"))
             x = torch.randn(y.shape[0], config.data.channels, config.data.image_size, config.data.image_size,
                             device=self.device)
-            x = simplified_loop(x, model, self.betas, args.eta, op, y, sigma_y, config)
-            img, psnr = ops.finalize_psnr(x, x_orig)
-            # the reference names the file with the stale loop variable j = -1 (:402); reproduced
-            save_image(img[0], os.path.join(args.image_folder, f"{idx_so_far + (-1)}_{0}.png"))
-            psnr_sum += float(psnr[0])
+            if K > 1:
+                tape = [torch.randn_like(x) for _ in range(n_iter)]      # what simplified_loop would draw for this image
+                pending.append((x, y.reshape(1, -1), tape, x_orig, idx_so_far))
+                if bi in group_ends:
+                    xf = simplified_loop(torch.cat([p[0] for p in pending], 0), model, self.betas, args.eta, op,
+                                         torch.cat([p[1] for p in pending], 0), sigma_y, config,
+                                         noise=FusedTape([p[2] for p in pending]))
+                    for j, p in enumerate(pending):
+                        finish(xf[j:j + 1].contiguous(), p[3], p[4])
+                    pending = []
+            else:
+                x = simplified_loop(x, model, self.betas, args.eta, op, y, sigma_y, config)
+                finish(x, x_orig, idx_so_far)
             idx_so_far += y.shape[0]
-            n_done += y.shape[0]
-            print("PSNR: %.2f" % (psnr_sum / n_done))
         psnr_sum, n_done = ddist.reduce_sum(psnr_sum, self.device), int(ddist.reduce_sum(n_done, self.device))
         if rank == 0:
             print("Total Average PSNR: %.2f" % (psnr_sum / max(n_done, 1)))

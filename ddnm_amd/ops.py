@@ -6,6 +6,7 @@ ddnm_amd/csrc.  Nothing in this module falls back to torch ops.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -809,6 +810,72 @@ class PhiloxNoise:
         return out
 
 
+class KeyedPhiloxNoise:
+    """Per-image in-kernel noise: image b of the batch draws with its own 64-bit key `keys[b]` and image counter
+    `image_ctrs[b]` (include/ddnm_hip.h::ddnm_randn_philox_keyed_f32), so that images from different loader batches --
+    different seeds -- share one sampler call and each still gets the noise it gets when restored alone.  The step
+    kernels' keyed entry points read the table [B][4] uint32 {key_lo, key_hi, image_ctr, 0}; `tensor(k, like)`
+    materialises the same values for any per-image length (also lengths that are not a multiple of 4)."""
+    XT_ITER = PhiloxNoise.XT_ITER
+
+    def __init__(self, keys, image_ctrs):
+        keys, image_ctrs = [int(k) for k in keys], [int(c) for c in image_ctrs]
+        if not keys or len(keys) != len(image_ctrs):
+            raise ValueError(f"KeyedPhiloxNoise: {len(keys)} keys for {len(image_ctrs)} image counters")
+        self.keys, self.image_ctrs = keys, image_ctrs
+        rows = [[k & 0xFFFFFFFF, (k >> 32) & 0xFFFFFFFF, c & 0xFFFFFFFF, 0] for k, c in zip(keys, image_ctrs)]
+        # uint32 bit patterns in an int32 tensor (the kernels only read the table)
+        self._host = torch.from_numpy(np.array(rows, dtype=np.uint32).view(np.int32))
+        self._dev = {}
+
+    @classmethod
+    def from_sources(cls, pairs):
+        """[(PhiloxNoise, image index within that source's batch), ...] -> one key row per pair: the fused batch of the
+        per-loader-batch sources, each image keeping its (seed, image_base + index) draw."""
+        pairs = list(pairs)
+        return cls([(p.seed_hi << 32) | p.seed_lo for p, _ in pairs], [p.image_base + int(i) for p, i in pairs])
+
+    concat = from_sources
+
+    def __len__(self):
+        return len(self.keys)
+
+    def table(self, device):
+        """The device key table (one host-to-device copy per device, kept for the life of the object)."""
+        device = torch.device(device)
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = self._host.to(device)
+        return t
+
+    def stamp(self, s, k):
+        s.rng_on, s.rng_iter = 1, int(k)
+        return s
+
+    def _check_batch(self, B):
+        if B != len(self.keys):
+            raise ValueError(f"KeyedPhiloxNoise holds {len(self.keys)} image keys, the batch has {B} images")
+
+    def tensor(self, k, like):
+        B = like.shape[0]
+        self._check_batch(B)
+        out = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+        check(_lib.lib().ddnm_randn_philox_keyed_f32(_p(out), B, out.numel() // B, _p(self.table(like.device)),
+                                                     int(k) & 0xFFFFFFFF, _stream()), "ddnm_randn_philox_keyed_f32")
+        return out
+
+
+def step_noise_args(name, noise, like):
+    """(entry point, noise argument) of step kernel `name` (e.g. "ddnm_step_color_f32") for `noise`: a tensor or None
+    (the unkeyed entry point, in-kernel draw per ddnm_step_scalars::rng_*), or a KeyedPhiloxNoise (the `_keyed_f32`
+    entry point with the device key table)."""
+    if isinstance(noise, KeyedPhiloxNoise):
+        noise._check_batch(like.shape[0])
+        return name[:-len("_f32")] + "_keyed_f32", _p(noise.table(like.device))
+    return name, _p(noise)
+
+
 def step_scalars(at, at_next, eta, lam=1.0, gamma=1.0):
     """Host-side scalar terms of one reverse step, evaluated in fp32 exactly like the reference
     (functions/svd_ddnm.py:57,63-65): `at`, `at_next` are fp32 torch scalars (alpha-bar)."""
@@ -847,8 +914,8 @@ def step_combine(x0, proj, apy, noise, et, s, out=None):
     chw = x0.numel() // B
     out = torch.empty_like(x0) if out is None else out
     ep, es = _et_args(et)
-    check(_lib.lib().ddnm_step_combine_f32(_p(x0), _p(proj), _p(apy), _p(noise), ep, es, _p(out), B, chw,
-                                           ctypes.byref(s), _stream()), "ddnm_step_combine_f32")
+    fn, nz = step_noise_args("ddnm_step_combine_f32", noise, x0)
+    check(getattr(_lib.lib(), fn)(_p(x0), _p(proj), _p(apy), nz, ep, es, _p(out), B, chw, ctypes.byref(s), _stream()), fn)
     return out
 
 

@@ -454,6 +454,31 @@ typedef struct ddnm_step_scalars {
 int ddnm_randn_philox_f32(float* out, int32_t B, int64_t chw, uint32_t seed_lo, uint32_t seed_hi, uint32_t iter,
                           uint32_t image_base, void* stream);
 
+/* Per-image Philox keys (a batch of independently seeded images in one launch).  rng_keys is a DEVICE table [B][4] of
+ * uint32 {key_lo, key_hi, image_ctr, 0} (16-byte aligned): image b draws element r of loop iteration `iter` as
+ * philox_normal4({key_lo, key_hi}, r / 4, iter, image_ctr)[r % 4] -- rows {seed_lo, seed_hi, image_base + b, 0}
+ * reproduce ddnm_randn_philox_f32 and the in-kernel draw of the unkeyed step entry points bit for bit.
+ * out [B][n]: any n >= 1; the last partial block of four writes its first n % 4 values only. */
+int ddnm_randn_philox_keyed_f32(float* out, int32_t B, int64_t n, const uint32_t* rng_keys, uint32_t iter,
+                                void* stream);
+/* Keyed step entry points: the arguments of the unkeyed ones with `rng_keys` in place of `noise`; the noise is always
+ * drawn in-kernel (s->rng_iter = loop iteration; s->rng_on and s->rng_seed_* / rng_image_base are not read). */
+int ddnm_step_combine_keyed_f32(const float* x0, const float* proj, const float* apy, const uint32_t* rng_keys,
+                                const float* et, int64_t et_bstride, float* xt_next, int32_t B, int64_t chw,
+                                const ddnm_step_scalars* s, void* stream);
+int ddnm_step_sr_avgpool_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                   const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                   int32_t r, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_color_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                              const float* y, float* x0, float* xt_next, int32_t B, int32_t HW,
+                              const float* w3_host, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_inpaint_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                const float* y, const int32_t* rank, int32_t n_kept, float* x0, float* xt_next,
+                                int32_t B, int32_t HW, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_denoise_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                const float* y, float* x0, float* xt_next, int32_t B, int64_t chw,
+                                const ddnm_step_scalars* s, void* stream);
+
 /* x0 only (first half of every step; also feeds time travel). */
 int ddnm_step_x0_f32(const float* xt, const float* et, int64_t et_bstride, float* x0, int32_t B, int64_t chw,
                      const ddnm_step_scalars* s, void* stream);
