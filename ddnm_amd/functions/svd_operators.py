@@ -33,10 +33,7 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
+from ..ops import _p
 
 
 def _img(vec, c, d):

@@ -27,14 +27,12 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from ..ops import _p
+from . import _net
 
 GN_EPS = 1e-5
 CIN_PAD = 32
 GRAD_SCALE_FP16 = 1024.0        # see EncoderUNetModel.convert_to_fp16
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def classifier_defaults():
@@ -66,7 +64,7 @@ def create_classifier(image_size, classifier_use_fp16, classifier_width, classif
 # module attribute (tests): False evaluates the timestep-independent prefix of a grouped pass for every replica
 SHARE_PREFIX = True
 
-class EncoderUNetModel:
+class EncoderUNetModel(_net.ADMNet):
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  channel_mult=(1, 2, 4, 8), use_fp16=False, num_head_channels=-1, use_scale_shift_norm=False,
                  resblock_updown=False, pool="adaptive", device=None, **kwargs):
@@ -77,38 +75,13 @@ class EncoderUNetModel:
         self.out_channels, self.head_ch = out_channels, num_head_channels
         self.time_embed_dim = 4 * model_channels
         self.device = torch.device("cuda") if device is None else torch.device(device)
-        mc = model_channels
-        ch = int(channel_mult[0] * mc)
-        self.input_blocks = [[("conv", in_channels, ch)]]
-        ds = 1
-        for level, mult in enumerate(channel_mult):
-            for _ in range(num_res_blocks):
-                layers = [("res", ch, int(mult * mc), "")]
-                ch = int(mult * mc)
-                if ds in attention_resolutions:
-                    layers.append(("attn", ch))
-                self.input_blocks.append(layers)
-            if level != len(channel_mult) - 1:
-                self.input_blocks.append([("res", ch, ch, "down")])
-                ds *= 2
-        self.middle_block = [("res", ch, ch, ""), ("attn", ch), ("res", ch, ch, "")]
+        ch, ds = self._plan_encoder(in_channels, model_channels, channel_mult, num_res_blocks, attention_resolutions)
         self.final_ch, self.pool_sp = ch, image_size // ds
-        off, self._film_off = 0, {}
-        for prefix, layers in self._walk():
-            for j, L in enumerate(layers):
-                if L[0] == "res":
-                    self._film_off[f"{prefix}.{j}"] = off
-                    off += 2 * L[2]
-        self.film_total = off
+        self._plan_film()
         self.w = None
         self.use_fp16 = False          # set by convert_to_fp16(), like the reference's runner (diffusion.py:176-177)
         self.h16 = False               # ... which selects the fp16-activation path unless DDNM_CLS_GEN1=1
         self._ws = None
-
-    def _walk(self):
-        for i, layers in enumerate(self.input_blocks):
-            yield f"input_blocks.{i}", layers
-        yield "middle_block", self.middle_block
 
     @property
     def max_group_batch(self):
@@ -118,12 +91,6 @@ class EncoderUNetModel:
         return ops.max_launch_batch(per_image)    # half of the addressable limit: 32 / 64 at 256 x 256 x 128
 
     # ------------------------------------------------------------------ nn.Module-like surface
-    def to(self, device):
-        return self
-
-    def eval(self):
-        return self
-
     def convert_to_fp16(self):
         """`classifier.convert_to_fp16()` (diffusion.py:176-177, unet.py:817-823): the torso runs the fp16-ACTIVATION
         path (`_forward_h16` / `_backward_h16`): activations and activation gradients fp16 NHWC in HBM, convolutions and
@@ -165,36 +132,12 @@ class EncoderUNetModel:
             if key + ".f16" not in self.w:
                 self.w[key + ".f16"] = ops.pack_conv_weight_f16(raw)
 
-    def _w16(self, key):
-        return self.w.get(key + ".f16") if self.use_fp16 else None
-
-    def parameters(self):
-        return iter(())
-
     def state_dict_shapes(self):
         s = OrderedDict()
         ted, mc = self.time_embed_dim, self.model_channels
         s["time_embed.0.weight"], s["time_embed.0.bias"] = (ted, mc), (ted,)
         s["time_embed.2.weight"], s["time_embed.2.bias"] = (ted, ted), (ted,)
-        for prefix, layers in self._walk():
-            for j, L in enumerate(layers):
-                n = f"{prefix}.{j}"
-                if L[0] == "conv":
-                    s[n + ".weight"], s[n + ".bias"] = (L[2], L[1], 3, 3), (L[2],)
-                elif L[0] == "res":
-                    cin, cout = L[1], L[2]
-                    s[n + ".in_layers.0.weight"], s[n + ".in_layers.0.bias"] = (cin,), (cin,)
-                    s[n + ".in_layers.2.weight"], s[n + ".in_layers.2.bias"] = (cout, cin, 3, 3), (cout,)
-                    s[n + ".emb_layers.1.weight"], s[n + ".emb_layers.1.bias"] = (2 * cout, ted), (2 * cout,)
-                    s[n + ".out_layers.0.weight"], s[n + ".out_layers.0.bias"] = (cout,), (cout,)
-                    s[n + ".out_layers.3.weight"], s[n + ".out_layers.3.bias"] = (cout, cout, 3, 3), (cout,)
-                    if cin != cout:
-                        s[n + ".skip_connection.weight"], s[n + ".skip_connection.bias"] = (cout, cin, 1, 1), (cout,)
-                else:
-                    c = L[1]
-                    s[n + ".norm.weight"], s[n + ".norm.bias"] = (c,), (c,)
-                    s[n + ".qkv.weight"], s[n + ".qkv.bias"] = (3 * c, c, 1), (3 * c,)
-                    s[n + ".proj_out.weight"], s[n + ".proj_out.bias"] = (c, c, 1), (c,)
+        self._layer_shapes(s)
         c = self.final_ch
         s["out.0.weight"], s["out.0.bias"] = (c,), (c,)
         s["out.2.positional_embedding"] = (c, self.pool_sp ** 2 + 1)
@@ -312,40 +255,13 @@ class EncoderUNetModel:
         return out
 
     def _attn(self, n, x, tape):
-        w = self.w
-        B, H, W, C = x.t.shape
-        T, hc = H * W, self.head_ch
-        nh = C // hc
         k = {} if tape is not None else None
-        gn = self._gn(x, n + ".norm", keep=k)
-        qkv = ops.conv2d(x, w[n + ".qkv.weight"], 3 * C, 1, gn=gn, gn_silu=False, bias=w[n + ".qkv.bias"],
-                         weight_f16=self._w16(n + ".qkv.weight"))
-        flat = qkv.view(-1)
-        S = torch.empty(B * nh, T, T, dtype=torch.float32, device=qkv.device)
-        ops.bgemm(flat, flat[hc:], S, T, T, hc, lda=3 * C, ldb=3 * C, ldc=T, transb=True, batch=B * nh, inner=nh,
-                  sA=(T * 3 * C, 3 * hc), sB=(T * 3 * C, 3 * hc), sC=(nh * T * T, T * T))
-        ops.softmax_rows_(S, B * nh * T, T, T, 1.0 / math.sqrt(hc))
-        o = torch.empty(B, H, W, C, dtype=torch.float32, device=qkv.device)
-        ops.bgemm(S, flat[2 * hc:], o, T, hc, T, lda=T, ldb=3 * C, ldc=C, transb=False, batch=B * nh, inner=nh,
-                  sA=(nh * T * T, T * T), sB=(T * 3 * C, 3 * hc), sC=(T * C, hc))
-        out = ops.conv2d(o, w[n + ".proj_out.weight"], C, 1, bias=w[n + ".proj_out.bias"], res=x, emit_stats=True,
-                         weight_f16=self._w16(n + ".proj_out.weight"))
+        out, qkv, S = self._attn32(n, x, self._gn(x, n + ".norm", keep=k), self.head_ch)
         if tape is not None:
             tape.append(("attn", n, x.t, qkv, S, k))
         return out
 
     # ------------------------------------------------------------------ fp16-activation forward (csrc/conv16.hip)
-    def _conv3_16(self, key, cout, x, gn, **kw):
-        """3x3 convolution (or data-gradient convolution) of an fp16 NHWC tensor on ddnm_conv16, the GroupNorm affine +
-        swish of `gn` fused into its loader; images too small for a pixel tile (8 x 8) go through im2col + one GEMM."""
-        w16 = self.w[key]
-        t = x.t if isinstance(x, ops.Act) else x
-        B, H, W, cin = t.shape
-        if ops.conv16_supported(B, H, W, cin, cout, 3):
-            return ops.conv16(x, w16, cout, 3, gn=gn, gn_silu=True, **kw)
-        col = ops.im2col16(x, None, gn, True)
-        return ops.conv16(col, w16.reshape(w16.shape[0], 1, -1), cout, 1, **kw)
-
     def _res_h16(self, n, L, x, film_all, tape, shared=None):
         w = self.w
         cin, cout, mode = L[1], L[2], L[3]
@@ -362,15 +278,15 @@ class EncoderUNetModel:
             gn1 = self._gn(x, n + ".in_layers.0", keep=k1)
             hp = ops.gn_apply16(x, None, gn1, True, pool=True)
             xs = ops.gn_apply16(x, None, None, False, pool=True)
-            h = self._conv3_16(n + ".in_layers.2.h16", cout, hp, None, bias=b1)
+            h = _net.conv3x3_16(w[n + ".in_layers.2.h16"], cout, hp, None, None, bias=b1)
         else:
             gn1 = self._gn(x, n + ".in_layers.0", keep=k1)
-            h = self._conv3_16(n + ".in_layers.2.h16", cout, x, gn1, bias=b1)
+            h = _net.conv3x3_16(w[n + ".in_layers.2.h16"], cout, x, None, gn1, bias=b1)
             if cin == cout:
                 xs = x.t
         gn2 = self._gn(h, n + ".out_layers.0", film=film_all[:, self._film_off[n]:], keep=k2)
         if xs is not None:
-            out = self._conv3_16(n + ".out_layers.3.h16", cout, h, gn2, bias=b2, res=xs)
+            out = _net.conv3x3_16(w[n + ".out_layers.3.h16"], cout, h, None, gn2, bias=b2, res=xs)
         else:
             B, H, W, _ = h.t.shape
             if ops.conv16_supported(B, H, W, cout, cout, 3):      # 1x1 shortcut fused as extra K chunks over the raw input
@@ -380,7 +296,7 @@ class EncoderUNetModel:
             else:
                 xs = ops.conv16(x.t, w[n + ".skip_connection.h16"], cout, 1, bias=w[n + ".skip_connection.bias"],
                                 emit_stats=False).t
-                out = self._conv3_16(n + ".out_layers.3.h16", cout, h, gn2, bias=b2, res=xs)
+                out = _net.conv3x3_16(w[n + ".out_layers.3.h16"], cout, h, None, gn2, bias=b2, res=xs)
         if tape is not None:
             tape.append(("res", n, L, x.t, h.t, k1, k2))
         return out
@@ -388,15 +304,10 @@ class EncoderUNetModel:
     def _attn_h16(self, n, x, tape):
         w = self.w
         B, H, W, C = x.t.shape
-        if self.head_ch != 64:
-            raise NotImplementedError("the fused attention kernels are built for 64-channel heads (the DDNM classifier)")
         k = {} if tape is not None else None
-        gn = self._gn(x, n + ".norm", keep=k)
-        a = ops.gn_apply16(x, None, gn, False)
-        qkv = ops.conv16(a, w[n + ".qkv.h16"], 3 * C, 1, bias=w[n + ".qkv.bias"], emit_stats=False).t
-        lse = None if tape is None else torch.empty(B, C // 64, H * W, dtype=torch.float32, device=qkv.device)
-        o = ops.attn16(qkv, C, lse=lse)
-        out = ops.conv16(o, w[n + ".proj_out.h16"], C, 1, bias=w[n + ".proj_out.bias"], res=x)
+        lse = None if tape is None else torch.empty(B, C // 64, H * W, dtype=torch.float32, device=x.t.device)
+        out, qkv, o = self._attn_block16(n, x, self._gn(x, n + ".norm", keep=k), self.head_ch, w[n + ".qkv.h16"],
+                                         w[n + ".proj_out.h16"], lse=lse)
         if tape is not None:
             tape.append(("attn", n, x.t, qkv, o, lse, k))
         return out
@@ -424,7 +335,7 @@ class EncoderUNetModel:
             n1 = "input_blocks.1.0"
             k1u = {}
             gn1 = self._gn(hu, n1 + ".in_layers.0", keep=k1u)
-            au = self._conv3_16(n1 + ".in_layers.2.h16", first[2], hu, gn1, bias=w[n1 + ".in_layers.2.bias"])
+            au = _net.conv3x3_16(w[n1 + ".in_layers.2.h16"], first[2], hu, None, gn1, bias=w[n1 + ".in_layers.2.bias"])
             h = ops.Act(rep(hu.t), None if hu.stats is None else rep(hu.stats), hu.tiles)
             a1 = ops.Act(rep(au.t), None if au.stats is None else rep(au.stats), au.tiles)
             k1 = {k: (rep(v) if torch.is_tensor(v) else v) for k, v in k1u.items()}
@@ -453,11 +364,7 @@ class EncoderUNetModel:
             return torch.cat([self.forward(x[i:i + mb], timesteps[i:i + mb]) for i in range(0, B, mb)], 0)
         self._workspace(B)
         L = _lib.lib()
-        t = timesteps.to(device=x.device, dtype=torch.float32).contiguous()
-        emb = ops.timestep_embedding(t, w["time.freq"], order=1)
-        emb = ops.linear(emb, w["time_embed.0.weight"], w["time_embed.0.bias"])
-        emb = ops.linear(emb, w["time_embed.2.weight"], w["time_embed.2.bias"], silu_in=True)
-        film_all = ops.linear(emb, w["film_cat.weight"], w["film_cat.bias"], silu_in=True)
+        film_all = self._film_all(self._time_embed(timesteps, x.device))
         if self.use_fp16 and self.h16:
             h = self._forward_h16(x, film_all, tape, replicas)
             return self._head(h, x, tape)
@@ -571,14 +478,14 @@ class EncoderUNetModel:
 
     def _res_bwd16(self, rec, dout):
         _, n, L, x, h1, k1, k2 = rec
+        w = self.w
         cin, cout, mode = L[1], L[2], L[3]
-        da2 = self._conv3_16(n + ".out_layers.3.dgrad.h16", cout, dout, None, emit_stats=False).t
+        da2 = _net.conv3x3_16(w[n + ".out_layers.3.dgrad.h16"], cout, dout, None, None, emit_stats=False).t
         dh1 = self._gn_bwd16(h1, da2, k2, True)
-        da1 = self._conv3_16(n + ".in_layers.2.dgrad.h16", cin, dh1, None, emit_stats=False).t
+        da1 = _net.conv3x3_16(w[n + ".in_layers.2.dgrad.h16"], cin, dh1, None, None, emit_stats=False).t
         if mode == "down":
             return self._gn_bwd16(x, da1, k1, True, add=dout, dA_ups=True, add_ups=True)
-        skip = dout if cin == cout else ops.conv16(dout, self.w[n + ".skip_connection.dgrad.h16"], cin, 1,
-                                                   emit_stats=False).t
+        skip = dout if cin == cout else ops.conv16(dout, w[n + ".skip_connection.dgrad.h16"], cin, 1, emit_stats=False).t
         return self._gn_bwd16(x, da1, k1, True, add=skip)
 
     def _attn_bwd16(self, rec, dout):

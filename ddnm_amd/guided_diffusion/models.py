@@ -33,6 +33,7 @@ from collections import OrderedDict
 import torch
 
 from .. import ops
+from . import _net
 
 GN_EPS = 1e-6          # models.py:33
 # DDNM_CONV_F32=mfma32: every convolution on the fp32 MFMA instruction (the pre-split engine; A/B switch)
@@ -51,7 +52,7 @@ class _Attn:
         self.name, self.c = name, c
 
 
-class Model:
+class Model(_net.GraphedNet):
     def __init__(self, config, device=None, split16=None):
         """`split16`: run the 3x3 / stride-1 layers on the split-fp16 kernel (None: the DDNM_CONV_F32 default above)."""
         self.config = config
@@ -72,7 +73,7 @@ class Model:
         self.device = torch.device("cuda") if device is None else torch.device(device)
         self._plan()
         self.w = None
-        self._ws, self._ws_by_stream, self._graphs = None, {}, None
+        self._reset_host_state()
 
     # ------------------------------------------------------------------ structure
     def _plan(self):
@@ -135,15 +136,6 @@ class Model:
         self.max_ch = max(rb.cin for rb in self.res_blocks)
 
     # ------------------------------------------------------------------ nn.Module-like surface
-    def to(self, device):
-        return self
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return iter(())
-
     def state_dict_shapes(self):
         """name -> shape of every tensor `load_state_dict` consumes; equals the reference
         `Model(config).state_dict()` (pinned in tests/test_host_logic.py against the golden key list)."""
@@ -194,20 +186,7 @@ class Model:
         return s
 
     def random_state_dict(self, seed=1234):
-        """Seeded random weights (no checkpoints exist offline): N(0, 1/fan_in) kernels, GN gamma near 1."""
-        g = torch.Generator().manual_seed(seed)
-        sd = OrderedDict()
-        for name, shape in self.state_dict_shapes().items():
-            if name.endswith(".weight") and len(shape) >= 2:
-                fan_in = 1
-                for d in shape[1:]:
-                    fan_in *= d
-                sd[name] = torch.randn(shape, generator=g) * fan_in ** -0.5
-            elif name.endswith(".weight"):
-                sd[name] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-            else:
-                sd[name] = 0.05 * torch.randn(shape, generator=g)
-        return sd
+        return _net.random_state_dict(self.state_dict_shapes(), seed)
 
     def load_state_dict(self, sd, strict=True):
         dev = self.device
@@ -303,11 +282,7 @@ class Model:
         freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1)))   # models.py:16-17
         w["temb.freq"] = freq.to(dev)
         self.w = w
-        self._ws = None
-        self._ws_by_stream = {}
-        if getattr(self, "_graphs", None) is not None:
-            self._graphs.reset()
-        self._auto_graphs = None
+        self._reset_host_state()
         return self
 
     def _guard_normalised_operands(self, sd, w):
@@ -336,23 +311,15 @@ class Model:
         return dropped
 
     # ------------------------------------------------------------------ forward
-    def _workspace(self, B):
-        """GroupNorm scratch of the current stream (one per stream: see ddnm_amd/graph.py)."""
-        key = torch.cuda.current_stream().cuda_stream
-        ent = self._ws_by_stream.get(key)
-        if ent is None or ent[1] < B:
-            r = self.resolution
-            max_partial = 0
-            # bound over the (HW, C) pairs that occur: C <= max_ch at every resolution
-            res = r
-            for _ in range(self.num_resolutions):
-                for c in (self.ch, self.max_ch):
-                    max_partial = max(max_partial, ops.gn_nchunk(res * res, c))
-                res //= 2
-            ent = (ops.GroupNormWorkspace(self.device, B, self.max_ch, B * max_partial * 32 * 2), B)
-            self._ws_by_stream[key] = ent
-        self._ws = ent[0]
-        return self._ws
+    def _max_gn_partials(self):
+        max_partial = 0
+        # bound over the (HW, C) pairs that occur: C <= max_ch at every resolution
+        res = self.resolution
+        for _ in range(self.num_resolutions):
+            for c in (self.ch, self.max_ch):
+                max_partial = max(max_partial, ops.gn_nchunk(res * res, c))
+            res //= 2
+        return max_partial
 
     def _gn(self, x0, x1, name, want_amax=False):
         return ops.group_norm_affine(x0, x1, self.w[name + ".weight"], self.w[name + ".bias"], GN_EPS, self._ws,
@@ -418,44 +385,12 @@ class Model:
         return ops.conv2d(o, w[n + ".proj_out.weight"], C, 1, bias=w[n + ".proj_out.bias"], res=x, emit_stats=True,
                           weight_s16=w.get(n + ".proj_out.s16"))
 
-    def enable_graphs(self, two_streams=False):
-        """Replay the forward from a captured hipGraph (ddnm_amd/graph.py)."""
-        from ..graph import GraphedForward
-        self._graphs = GraphedForward(lambda x, t, y: self._forward_eager(x, t), two_streams=two_streams)
-        return self
-
-    def disable_graphs(self):
-        self._graphs = None
-        return self
-
-    def auto_graphs(self, max_batch=2):
-        """Replay forwards of at most `max_batch` images from a captured hipGraph, decided per call (0: never).  The
-        reference's shipped configs sample with batch_size 1 (configs/celeba_hq.yml:34-35); a forward is ~250 launches
-        whose host cost (~15 us each through ctypes) then exceeds their GPU time, and `cudnn.benchmark` was the
-        reference's own small-batch lever (main.py:145).  The runner (`Diffusion`) switches this on."""
-        self.auto_graph_max_batch = int(max_batch)
-        self._auto_graphs = None
-        return self
-
     @property
     def max_forward_batch(self):
         """Chunk size of forward(): the largest activation is `ch` channels of fp32 at full resolution."""
         return ops.max_launch_batch(self.resolution * self.resolution * self.ch * 4)
 
-    def forward(self, x, t):
-        mb = self.max_forward_batch
-        if x.shape[0] > mb:          # more images than one launch can address: micro-batches, concatenated
-            return torch.cat([self.forward(x[i:i + mb], t[i:i + mb]) for i in range(0, x.shape[0], mb)], 0)
-        if getattr(self, "_graphs", None) is not None:
-            return self._graphs(x, t, None)
-        if x.shape[0] <= getattr(self, "auto_graph_max_batch", 0):
-            if getattr(self, "_auto_graphs", None) is None:
-                from ..graph import GraphedForward
-                self._auto_graphs = GraphedForward(lambda x_, t_, y_: self._forward_eager(x_, t_), two_streams=False)
-            return self._auto_graphs(x, t, None)
-        return self._forward_eager(x, t)
-
-    def _forward_eager(self, x, t):
+    def _forward_eager(self, x, t, y=None):
         if self.w is None:
             raise RuntimeError("load_state_dict() must be called before forward()")
         assert x.shape[2] == x.shape[3] == self.resolution

@@ -30,6 +30,7 @@ from collections import OrderedDict
 import torch
 
 from .. import ops
+from . import _net
 
 GN_EPS = 1e-5          # torch.nn.GroupNorm default, guided_diffusion/nn.py:93-100
 CIN_PAD = 32
@@ -58,7 +59,9 @@ def create_model(image_size, num_channels, num_res_blocks, channel_mult="", lear
                      resblock_updown=resblock_updown, use_new_attention_order=use_new_attention_order)
 
 
-class UNetModel:
+class UNetModel(_net.ADMNet, _net.GraphedNet):
+    TWO_STREAMS = True
+
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks, attention_resolutions,
                  channel_mult=(1, 2, 4, 8), num_classes=None, num_heads=1, num_head_channels=-1,
                  use_scale_shift_norm=False, resblock_updown=False, use_new_attention_order=False, device=None,
@@ -75,23 +78,8 @@ class UNetModel:
         self.time_embed_dim = 4 * model_channels
         self.device = torch.device("cuda") if device is None else torch.device(device)
         mc = model_channels
-        ch = int(channel_mult[0] * mc)
-        self.input_blocks = [[("conv", in_channels, ch)]]
-        chans = [ch]
-        ds = 1
-        for level, mult in enumerate(channel_mult):
-            for _ in range(num_res_blocks):
-                layers = [("res", ch, int(mult * mc), "")]
-                ch = int(mult * mc)
-                if ds in attention_resolutions:
-                    layers.append(("attn", ch))
-                self.input_blocks.append(layers)
-                chans.append(ch)
-            if level != len(channel_mult) - 1:
-                self.input_blocks.append([("res", ch, ch, "down")])
-                chans.append(ch)
-                ds *= 2
-        self.middle_block = [("res", ch, ch, ""), ("attn", ch), ("res", ch, ch, "")]
+        ch, ds = self._plan_encoder(in_channels, mc, channel_mult, num_res_blocks, attention_resolutions)
+        chans = [layers[0][2] for layers in self.input_blocks]        # channels every input block leaves on the skip stack
         self.output_blocks = []
         for level, mult in list(enumerate(channel_mult))[::-1]:
             for i in range(num_res_blocks + 1):
@@ -105,39 +93,13 @@ class UNetModel:
                     ds //= 2
                 self.output_blocks.append(layers)
         self.final_ch = ch
-        # FiLM projection layout: one slice [2*cout] per ResBlock, in execution order
-        self._res_names = []
-        off = 0
-        self._film_off = {}
-        for prefix, layers in self._walk():
-            for j, L in enumerate(layers):
-                if L[0] == "res":
-                    n = f"{prefix}.{j}"
-                    self._film_off[n] = off
-                    off += 2 * L[2]
-                    self._res_names.append((n, L))
-        self.film_total = off
-        self.max_ch = max(L[1] for _, L in self._res_names)
+        self._plan_film()
+        self.max_ch = max(L[1] for _, layers in self._walk() for L in layers if L[0] == "res")
         self.w = None
-        self._ws = None
-        self._ws_by_stream = {}
-        self._graphs = None
+        self._reset_host_state()
         self.use_fp16 = False
 
-    def _walk(self):
-        for i, layers in enumerate(self.input_blocks):
-            yield f"input_blocks.{i}", layers
-        yield "middle_block", self.middle_block
-        for i, layers in enumerate(self.output_blocks):
-            yield f"output_blocks.{i}", layers
-
     # ------------------------------------------------------------------ nn.Module-like surface
-    def to(self, device):
-        return self
-
-    def eval(self):
-        return self
-
     def convert_to_fp16(self):
         """The reference's `model.convert_to_fp16()` (diffusion.py:145-146, unet.py:619-625): the 3x3 convs
         of the torso run on fp16 MFMA operands with fp32 accumulation (csrc/conv_igemm_f16.hip); GroupNorm,
@@ -186,9 +148,6 @@ class UNetModel:
                 w[key + ".h16"] = ops.pack_conv_weight16(raw)
         w["h16.ready"] = True
 
-    def parameters(self):
-        return iter(())
-
     def state_dict_shapes(self):
         s = OrderedDict()
         ted, mc = self.time_embed_dim, self.model_channels
@@ -196,43 +155,13 @@ class UNetModel:
         s["time_embed.2.weight"], s["time_embed.2.bias"] = (ted, ted), (ted,)
         if self.num_classes is not None:
             s["label_emb.weight"] = (self.num_classes, ted)
-        for prefix, layers in self._walk():
-            for j, L in enumerate(layers):
-                n = f"{prefix}.{j}"
-                if L[0] == "conv":
-                    s[n + ".weight"], s[n + ".bias"] = (L[2], L[1], 3, 3), (L[2],)
-                elif L[0] == "res":
-                    cin, cout = L[1], L[2]
-                    s[n + ".in_layers.0.weight"], s[n + ".in_layers.0.bias"] = (cin,), (cin,)
-                    s[n + ".in_layers.2.weight"], s[n + ".in_layers.2.bias"] = (cout, cin, 3, 3), (cout,)
-                    s[n + ".emb_layers.1.weight"], s[n + ".emb_layers.1.bias"] = (2 * cout, ted), (2 * cout,)
-                    s[n + ".out_layers.0.weight"], s[n + ".out_layers.0.bias"] = (cout,), (cout,)
-                    s[n + ".out_layers.3.weight"], s[n + ".out_layers.3.bias"] = (cout, cout, 3, 3), (cout,)
-                    if cin != cout:
-                        s[n + ".skip_connection.weight"], s[n + ".skip_connection.bias"] = (cout, cin, 1, 1), (cout,)
-                else:
-                    c = L[1]
-                    s[n + ".norm.weight"], s[n + ".norm.bias"] = (c,), (c,)
-                    s[n + ".qkv.weight"], s[n + ".qkv.bias"] = (3 * c, c, 1), (3 * c,)
-                    s[n + ".proj_out.weight"], s[n + ".proj_out.bias"] = (c, c, 1), (c,)
+        self._layer_shapes(s)
         s["out.0.weight"], s["out.0.bias"] = (self.final_ch,), (self.final_ch,)
         s["out.2.weight"], s["out.2.bias"] = (self.out_channels, self.final_ch, 3, 3), (self.out_channels,)
         return s
 
     def random_state_dict(self, seed=1234):
-        g = torch.Generator().manual_seed(seed)
-        sd = OrderedDict()
-        for name, shape in self.state_dict_shapes().items():
-            if name.endswith(".weight") and len(shape) >= 2:
-                fan_in = 1
-                for d in shape[1:]:
-                    fan_in *= d
-                sd[name] = torch.randn(shape, generator=g) * fan_in ** -0.5
-            elif name.endswith(".weight"):
-                sd[name] = 1.0 + 0.1 * torch.randn(shape, generator=g)
-            else:
-                sd[name] = 0.05 * torch.randn(shape, generator=g)
-        return sd
+        return _net.random_state_dict(self.state_dict_shapes(), seed)
 
     def load_state_dict(self, sd, strict=True):
         dev = self.device
@@ -294,33 +223,18 @@ class UNetModel:
         half = self.model_channels // 2
         w["time.freq"] = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half).to(dev)
         self.w = w
-        self._ws = None
-        self._ws_by_stream = {}
-        if self._graphs is not None:
-            self._graphs.reset()
-        self._auto_graphs = None
+        self._reset_host_state()
         if self.use_fp16:
             self._pack_h16()
         return self
 
-    def _w16(self, key):
-        return self.w.get(key + ".f16") if self.use_fp16 else None
-
     # ------------------------------------------------------------------ forward
-    def _workspace(self, B):
-        """GroupNorm scratch of the current stream (the affine of one GroupNorm is consumed by the next launch on the
-        same stream; the two half-batch streams of a captured forward each own one)."""
-        key = torch.cuda.current_stream().cuda_stream
-        ent = self._ws_by_stream.get(key)
-        if ent is None or ent[1] < B:
-            res, mp = self.image_size, 0
-            while res >= 8:
-                mp = max(mp, ops.gn_nchunk(res * res, min(self.max_ch, 4096)))
-                res //= 2
-            ent = (ops.GroupNormWorkspace(self.device, B, self.max_ch, B * mp * 32 * 2), B)
-            self._ws_by_stream[key] = ent
-        self._ws = ent[0]
-        return self._ws
+    def _max_gn_partials(self):
+        res, mp = self.image_size, 0
+        while res >= 8:
+            mp = max(mp, ops.gn_nchunk(res * res, min(self.max_ch, 4096)))
+            res //= 2
+        return mp
 
     def _gn(self, x0, x1, name, film=None):
         if x1 is None and isinstance(x0, ops.Act) and x0.gn is not None and x0.gn[2] == name \
@@ -376,24 +290,8 @@ class UNetModel:
                           weight_f16=self._w16(n + ".out_layers.3.weight"))
 
     def _attn(self, n, x):
-        w = self.w
-        B, H, W, C = x.t.shape
-        T = H * W
-        hc = self.num_head_channels if self.num_head_channels != -1 else C // self.num_heads
-        nh = C // hc
-        gn = self._gn(x, None, n + ".norm")
-        qkv = ops.conv2d(x, w[n + ".qkv.weight"], 3 * C, 1, gn=gn, gn_silu=False, bias=w[n + ".qkv.bias"],
-                         weight_f16=self._w16(n + ".qkv.weight"))
-        flat = qkv.view(-1)
-        S = torch.empty(B * nh, T, T, dtype=torch.float32, device=qkv.device)
-        ops.bgemm(flat, flat[hc:], S, T, T, hc, lda=3 * C, ldb=3 * C, ldc=T, transb=True, batch=B * nh, inner=nh,
-                  sA=(T * 3 * C, 3 * hc), sB=(T * 3 * C, 3 * hc), sC=(nh * T * T, T * T))
-        ops.softmax_rows_(S, B * nh * T, T, T, 1.0 / math.sqrt(hc))      # (q*s).(k*s), s = hc^-1/4
-        o = torch.empty(B, H, W, C, dtype=torch.float32, device=qkv.device)
-        ops.bgemm(S, flat[2 * hc:], o, T, hc, T, lda=T, ldb=3 * C, ldc=C, transb=False, batch=B * nh, inner=nh,
-                  sA=(nh * T * T, T * T), sB=(T * 3 * C, 3 * hc), sC=(T * C, hc))
-        return ops.conv2d(o, w[n + ".proj_out.weight"], C, 1, bias=w[n + ".proj_out.bias"], res=x, emit_stats=True,
-                          weight_f16=self._w16(n + ".proj_out.weight"))
+        hc = self.num_head_channels if self.num_head_channels != -1 else x.t.shape[3] // self.num_heads
+        return self._attn32(n, x, self._gn(x, None, n + ".norm"), hc)[0]
 
     def _run(self, prefix, layers, h, skip, film_all):
         for j, L in enumerate(layers):
@@ -407,21 +305,6 @@ class UNetModel:
         return h
 
     # ------------------------------------------------------------------ fp16-activation forward (csrc/conv16.hip)
-    def _conv3x3_16(self, key, cout, x0, x1, gn, silu=True, **kw):
-        """3x3 convolution of act(concat(x0, x1)) on ddnm_conv16 with the GroupNorm affine + swish and the concat fused
-        into its loader; images too small for a
-        pixel tile (8x8) go through im2col + one GEMM with K = 9*Cin."""
-        w16 = self.w[key + ".h16"]
-        B, H, W, _ = x0.t.shape
-        cin = x0.t.shape[3] + (0 if x1 is None else x1.t.shape[3])
-        ups = kw.get("ups", False)
-        Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
-        if ops.conv16_supported(B, Ho, Wo, cin, cout, 3, ups=ups):
-            return ops.conv16(x0, w16, cout, 3, src1=x1, gn=gn, gn_silu=silu, **kw)
-        assert not ups and kw.get("skip") is None
-        col = ops.im2col16(x0, x1, gn, silu)
-        return ops.conv16(col, w16.reshape(w16.shape[0], 1, -1), cout, 1, **kw)
-
     def _fin(self, name, film=None):
         """What a producing convolution needs to finalize the GroupNorm `name` over its own output in its split-K
         reduction pass (ops.conv16 `fin=`; no effect on launches that are not split)."""
@@ -438,43 +321,37 @@ class UNetModel:
         film = film_all[:, self._film_off[n]:]
         gn1 = self._gn(x0, x1, n + ".in_layers.0")
         b1, b2 = w[n + ".in_layers.2.bias"], w[n + ".out_layers.3.bias"]
-        k1, k2 = n + ".in_layers.2.weight", n + ".out_layers.3.weight"
+        k1, k2 = w[n + ".in_layers.2.weight.h16"], w[n + ".out_layers.3.weight.h16"]
         fin2 = self._fin(n + ".out_layers.0", film)
         if mode == "down":          # AvgPool2d on both branches (unet.py:237-242)
             hp = ops.Act(ops.gn_apply16(x0, None, gn1, True, pool=True))
             xs = ops.gn_apply16(x0, None, None, False, pool=True)
-            h = self._conv3x3_16(k1, cout, hp, None, None, bias=b1, fin=fin2)
+            h = _net.conv3x3_16(k1, cout, hp, None, None, bias=b1, fin=fin2)
             gn2 = self._gn(h, None, n + ".out_layers.0", film=film)
-            return self._conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=xs, fin=next_fin)
+            return _net.conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=xs, fin=next_fin)
         if mode == "up":            # nearest x2 on both branches: operand through `ups`, residual through `res_ups`
-            h = self._conv3x3_16(k1, cout, x0, None, gn1, bias=b1, ups=True, fin=fin2)
+            h = _net.conv3x3_16(k1, cout, x0, None, gn1, bias=b1, ups=True, fin=fin2)
             gn2 = self._gn(h, None, n + ".out_layers.0", film=film)
-            return self._conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=x0, res_ups=True, fin=next_fin)
-        h = self._conv3x3_16(k1, cout, x0, x1, gn1, bias=b1, fin=fin2)
+            return _net.conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=x0, res_ups=True, fin=next_fin)
+        h = _net.conv3x3_16(k1, cout, x0, x1, gn1, bias=b1, fin=fin2)
         gn2 = self._gn(h, None, n + ".out_layers.0", film=film)
         if cin == cout:
             assert x1 is None
-            return self._conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=x0, fin=next_fin)
+            return _net.conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=x0, fin=next_fin)
         B, H, W, _ = h.t.shape
         if ops.conv16_supported(B, H, W, cout, cout, 3):      # 1x1 shortcut fused as extra K chunks over the raw input
-            return self._conv3x3_16(k2, cout, h, None, gn2, bias=w[n + ".out_plus_skip.bias"], skip=(x0, x1),
-                                    skip_weight=w[n + ".skip_connection.weight.h16.flat"], fin=next_fin)
+            return _net.conv3x3_16(k2, cout, h, None, gn2, bias=w[n + ".out_plus_skip.bias"], skip=(x0, x1),
+                                   skip_weight=w[n + ".skip_connection.weight.h16.flat"], fin=next_fin)
         raw = x0.t if x1 is None else ops.gn_apply16(x0, x1, None, False)      # materialised concat of the raw tensors
         xs = ops.conv16(raw, w[n + ".skip_connection.weight.h16"], cout, 1, bias=w[n + ".skip_connection.bias"],
                         emit_stats=False)
-        return self._conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=xs, fin=next_fin)
+        return _net.conv3x3_16(k2, cout, h, None, gn2, bias=b2, res=xs, fin=next_fin)
 
     def _attn16(self, n, x):
         w = self.w
-        C = x.t.shape[3]
-        hc = self.num_head_channels if self.num_head_channels != -1 else C // self.num_heads
-        if hc != 64:
-            raise NotImplementedError("the fused attention kernel is built for 64-channel heads (all DDNM configs)")
-        gn = self._gn(x, None, n + ".norm")
-        a = ops.gn_apply16(x, None, gn, False)
-        qkv = ops.conv16(a, w[n + ".qkv.weight.h16"], 3 * C, 1, bias=w[n + ".qkv.bias"], emit_stats=False)
-        o = ops.attn16(qkv.t, C)
-        return ops.conv16(o, w[n + ".proj_out.weight.h16"], C, 1, bias=w[n + ".proj_out.bias"], res=x)
+        hc = self.num_head_channels if self.num_head_channels != -1 else x.t.shape[3] // self.num_heads
+        return self._attn_block16(n, x, self._gn(x, None, n + ".norm"), hc, w[n + ".qkv.weight.h16"],
+                                  w[n + ".proj_out.weight.h16"])[0]
 
     def _run16(self, prefix, layers, h, skip, film_all, next_fin=None):
         for j, L in enumerate(layers):
@@ -511,25 +388,6 @@ class UNetModel:
         a = ops.gn_apply16(h, None, gn, True)
         return ops.conv2d(a.float(), w["out.2.weight"], self.out_channels, 3, bias=w["out.2.bias"], out_nchw=True)
 
-    def enable_graphs(self, two_streams=True):
-        """Replay the forward from a captured hipGraph (one per batch shape): no per-launch host work, and with
-        `two_streams` the two halves of the batch run as concurrent branches of the graph (ddnm_amd/graph.py)."""
-        from ..graph import GraphedForward
-        self._graphs = GraphedForward(self._forward_eager, two_streams=two_streams)
-        return self
-
-    def disable_graphs(self):
-        self._graphs = None
-        return self
-
-    def auto_graphs(self, max_batch=2):
-        """Replay forwards of at most `max_batch` images from a captured hipGraph, decided per call (0: never): the
-        reference's shipped configs sample with batch_size 1 (configs/imagenet_256.yml:42), where the ~300 launches of
-        a forward cost more host time than GPU time.  The runner (`Diffusion`) switches this on."""
-        self.auto_graph_max_batch = int(max_batch)
-        self._auto_graphs = None
-        return self
-
     @property
     def max_forward_batch(self):
         """Chunk size of forward(): the largest activation is `model_channels` channels at full resolution (the skip
@@ -542,31 +400,17 @@ class UNetModel:
             raise RuntimeError("load_state_dict() must be called before forward()")
         assert (y is not None) == (self.num_classes is not None), \
             "must specify y if and only if the model is class-conditional"
-        mb = self.max_forward_batch
-        if x.shape[0] > mb:          # more images than one launch can address: micro-batches, concatenated
-            return torch.cat([self.forward(x[i:i + mb], timesteps[i:i + mb], None if y is None else y[i:i + mb])
-                              for i in range(0, x.shape[0], mb)], 0)
-        if self._graphs is not None:
-            return self._graphs(x, timesteps, y)
-        if x.shape[0] <= getattr(self, "auto_graph_max_batch", 0):
-            if getattr(self, "_auto_graphs", None) is None:
-                from ..graph import GraphedForward
-                self._auto_graphs = GraphedForward(self._forward_eager, two_streams=False)
-            return self._auto_graphs(x, timesteps, y)
-        return self._forward_eager(x, timesteps, y)
+        return super().forward(x, timesteps, y)
 
     def _forward_eager(self, x, timesteps, y=None):
         w = self.w
         B = x.shape[0]
         self._workspace(B)
-        t = timesteps.to(device=x.device, dtype=torch.float32).contiguous()
-        emb = ops.timestep_embedding(t, w["time.freq"], order=1)
-        emb = ops.linear(emb, w["time_embed.0.weight"], w["time_embed.0.bias"])
-        emb = ops.linear(emb, w["time_embed.2.weight"], w["time_embed.2.bias"], silu_in=True)
+        emb = self._time_embed(timesteps, x.device)
         if self.num_classes is not None:
             assert y.shape == (B,)
             ops.embedding_add_(emb, w["label_emb.weight"], y)
-        film_all = ops.linear(emb, w["film_cat.weight"], w["film_cat.bias"], silu_in=True)
+        film_all = self._film_all(emb)
         if self.use_fp16 and os.environ.get("DDNM_ADM_GEN1") != "1":
             return self._forward16(x, film_all)
         if self.use_fp16:

@@ -24,15 +24,12 @@ import torch
 
 from .. import _lib, ops
 from .._lib import check
+from ..ops import _p
 from .respace import respaced_betas
 from .scheduler import get_schedule_jump
 
 TILE, SHIFT = 256, 128
 _THIRD = (ctypes.c_float * 3)(1 / 3, 1 / 3, 1 / 3)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps, use_scale):

@@ -56,6 +56,22 @@ def set_kernel_timer(t):
     _timer = t
 
 
+def _launch(fn, d, label, record):
+    """Checked launch of `fn(descriptor, stream)`.  With a `KernelTimer` installed the launch is bracketed by two events
+    on the launch stream and recorded: `record()` -> (variant, flops, shape tuple of KernelTimer.shapes) is called only
+    then (resolving the variant of some kernel families costs an extra library call)."""
+    if _timer is None:
+        check(fn(ctypes.byref(d), _stream()), label)
+        return
+    variant, flops, shape = record()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(fn(ctypes.byref(d), _stream()), label)
+    e1.record()
+    _timer.records.append((variant, flops, e0, e1))
+    _timer.shapes.append(shape)
+
+
 def max_launch_batch(per_image_bytes, margin=2):
     """Largest batch whose biggest activation stays `margin` times below the 2 GiB one convolution launch can address
     (32-bit byte offsets of the raw buffer descriptors, csrc/conv_common.h::conv_sizes_addressable): the models split a
@@ -111,12 +127,23 @@ class Act:
         self.gn = gn
 
 
-def conv_fuses_skip(B, H, W, cin, cout):
-    """True when a 3x3 / stride-1 conv of this shape runs on the halo kernel, i.e. can take a fused shortcut."""
+def tensor_of(x):
+    """The tensor of an `Act`; a tensor (or None) as it is."""
+    return x.t if isinstance(x, Act) else x
+
+
+def _shape_desc(B, H, W, cin, cout, ksize=3, stride=1):
+    """Shape-only `ConvDesc` of a one-source conv over a [B, H, W, cin] INPUT ("same" padding at stride 1, none at
+    stride 2), for the planners' support queries."""
     d = ConvDesc()
     d.B, d.Hin, d.Win, d.C0, d.C1, d.Cout = B, H, W, cin, 0, cout
-    d.ksize, d.stride, d.pad, d.Ho, d.Wo = 3, 1, 1, H, W
-    return _lib.lib().ddnm_conv2d_f32_fuses_skip(ctypes.byref(d)) == 1
+    d.ksize, d.stride, d.pad, d.Ho, d.Wo = ksize, stride, (ksize // 2 if stride == 1 else 0), H // stride, W // stride
+    return d
+
+
+def conv_fuses_skip(B, H, W, cin, cout):
+    """True when a 3x3 / stride-1 conv of this shape runs on the halo kernel, i.e. can take a fused shortcut."""
+    return _lib.lib().ddnm_conv2d_f32_fuses_skip(ctypes.byref(_shape_desc(B, H, W, cin, cout))) == 1
 
 
 def pack_skip_weight(w, f16=False):
@@ -157,20 +184,14 @@ def pack_conv_weight_s16(w, scale):
 
 def conv_runs_s16(B, H, W, cin, cout, ups=False):
     """True when a 3x3 / stride-1 conv of this OUTPUT shape takes the split-fp16 kernel (given split-packed weights)."""
-    d = ConvDesc()
-    d.B, d.Hin, d.Win, d.C0, d.C1, d.Cout = B, H, W, cin, 0, cout
-    d.ksize, d.stride, d.pad, d.Ho, d.Wo = 3, 1, 1, H, W
-    return _lib.lib().ddnm_conv3x3_s16_supported(ctypes.byref(d)) == 1
+    return _lib.lib().ddnm_conv3x3_s16_supported(ctypes.byref(_shape_desc(B, H, W, cin, cout))) == 1
 
 
 def conv_runs_s16_gather(B, H, W, cin, cout, ksize=3, stride=1):
     """True when a conv of this INPUT shape takes the gather form of the split-fp16 arithmetic (no fused shortcut)."""
     if _NO_S16_GATHER:
         return False
-    d = ConvDesc()
-    d.B, d.Hin, d.Win, d.C0, d.C1, d.Cout = B, H, W, cin, 0, cout
-    d.ksize, d.stride, d.pad, d.Ho, d.Wo = ksize, stride, (ksize // 2 if stride == 1 else 0), H // stride, W // stride
-    return _lib.lib().ddnm_conv_gather_s16_supported(ctypes.byref(d)) == 1
+    return _lib.lib().ddnm_conv_gather_s16_supported(ctypes.byref(_shape_desc(B, H, W, cin, cout, ksize, stride))) == 1
 
 
 _S16_ACT_SCALE = None
@@ -186,10 +207,8 @@ def _s16_act_scale():
 
 def conv_runs_f16(B, H, W, cin, cout, ksize=3):
     """True when a stride-1 conv of this shape takes the fp16-operand kernel (given packed fp16 weights)."""
-    d = ConvDesc()
-    d.B, d.Hin, d.Win, d.C0, d.C1, d.Cout = B, H, W, cin, 0, cout
-    d.ksize, d.stride, d.pad, d.Ho, d.Wo = ksize, 1, ksize // 2, H, W
     L = _lib.lib()
+    d = _shape_desc(B, H, W, cin, cout, ksize)
     return (L.ddnm_conv3x3_f16_supported if ksize == 3 else L.ddnm_conv1x1_f16_supported)(ctypes.byref(d)) == 1
 
 
@@ -222,9 +241,9 @@ def amax_bound(a0, a1=None):
         if isinstance(a, Act) and a.stats is not None:
             B = a.t.shape[0]
             return a.stats, a.stats.numel() // B, 1
-        t = a.t if isinstance(a, Act) else a
+        t = tensor_of(a)
         return _f32c(t, "amax source"), t.numel() // t.shape[0], 0
-    t0 = a0.t if isinstance(a0, Act) else a0
+    t0 = tensor_of(a0)
     B = t0.shape[0]
     p0, n0, k0 = src(a0)
     p1, n1, k1 = src(a1)
@@ -247,9 +266,7 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     are range-guarded: `raw_amax` = their [B][AMAX_N] bound (amax_bound / group_norm_affine(want_amax=True)); when it is
     not supplied it is computed here from the producers' partials or the tensors."""
     a_src0, a_src1 = src0, src1                 # (possibly `Act`s: their partials feed the operand bound)
-    src0 = src0.t if isinstance(src0, Act) else src0
-    src1 = src1.t if isinstance(src1, Act) else src1
-    res = res.t if isinstance(res, Act) else res
+    src0, src1, res = tensor_of(src0), tensor_of(src1), tensor_of(res)
     B, Hs, Ws, C0 = src0.shape
     C1 = 0 if src1 is None else src1.shape[3]
     Hin, Win = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
@@ -275,15 +292,9 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     L = _lib.lib()
     if out_nchw and cout <= 4 and skip is None and weight_f16 is None and L.ddnm_conv3x3_small_cout_f32_supported(ctypes.byref(d)) == 1:
         # the network's 3-channel output convolution: HBM-bound vector-ALU kernel (csrc/conv_small_f32.hip)
-        if _timer is None:
-            check(L.ddnm_conv3x3_small_cout_f32(ctypes.byref(d), _stream()), "ddnm_conv3x3_small_cout_f32")
-        else:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            check(L.ddnm_conv3x3_small_cout_f32(ctypes.byref(d), _stream()), "ddnm_conv3x3_small_cout_f32")
-            e1.record()
-            _timer.records.append(("conv3x3_small_cout_f32", 2.0 * B * Ho * Wo * cout * 9 * C0, e0, e1))
-            _timer.shapes.append((B, Ho, Wo, C0, cout, 3, 1, 0, 0, gn is not None, False))
+        _launch(L.ddnm_conv3x3_small_cout_f32, d, "ddnm_conv3x3_small_cout_f32",
+                lambda: ("conv3x3_small_cout_f32", 2.0 * B * Ho * Wo * cout * 9 * C0,
+                         (B, Ho, Wo, C0, cout, 3, 1, 0, 0, gn is not None, False)))
         return Act(out, None, 0) if emit_stats else out
     # fp16-operand MFMA path (the reference's use_fp16 torso) when packed fp16 weights are supplied and the
     # shape qualifies; everything else runs the exact-fp32 kernels
@@ -292,8 +303,7 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
         # the whole shortcut part of the descriptor is filled BEFORE the support queries below, so that every planner
         # sees the descriptor the launch will see (some key on the pointer, some on the channel counts);
         # skip_weight is chosen further down, once the kernel family is known
-        s0 = skip[0].t if isinstance(skip[0], Act) else skip[0]
-        s1 = None if skip[1] is None else (skip[1].t if isinstance(skip[1], Act) else skip[1])
+        s0, s1 = tensor_of(skip[0]), tensor_of(skip[1])
         d.skip0, d.skip1 = _p(s0), _p(s1)
         d.SC0, d.SC1 = s0.shape[3], (0 if s1 is None else s1.shape[3])
     s16 = (weight_s16 is not None and weight_f16 is None and ksize == 3 and stride == 1
@@ -371,9 +381,8 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     if need > 0:
         ws = _conv_workspace(src0.device, need)
         d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
-    if _timer is None:
-        check(fn_run(ctypes.byref(d), _stream()), "ddnm_conv2d")
-    else:
+
+    def record():
         if f16_1x1:
             variant = "conv1x1_f16<256x128>"
         elif f16:
@@ -386,14 +395,10 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
             tn = L.ddnm_conv2d_f32_tile_n(ctypes.byref(d))
             kind = "conv3x3_halo_f32" if (ksize == 3 and stride == 1) else "conv_gather_f32"
             variant = kind + {128: "<128x128>", 64: "<64x64>", 32: "<128x32>"}[tn]
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(fn_run(ctypes.byref(d), _stream()), "ddnm_conv2d")
-        e1.record()
         flops = 2.0 * B * Ho * Wo * cout * (ksize * ksize * (C0 + C1) + d.SC0 + d.SC1)      # + fused 1x1 shortcut
-        _timer.records.append((variant, flops, e0, e1))
-        _timer.shapes.append((B, Ho, Wo, C0 + C1, cout, ksize, stride, int(ups), d.SC0 + d.SC1, gn is not None,
-                              res is not None))
+        return variant, flops, (B, Ho, Wo, C0 + C1, cout, ksize, stride, int(ups), d.SC0 + d.SC1, gn is not None,
+                                res is not None)
+    _launch(fn_run, d, "ddnm_conv2d", record)
     if _S16_CHECK and (s16 or s16g) and not bool(torch.isfinite(out).all()):
         raise FloatingPointError(f"split-fp16 launch produced non-finite values (B={B}, {Hin}x{Win}, Cin={C0 + C1}, "
                                  f"Cout={cout}, k={ksize}): an operand left fp16 range; DDNM_CONV_F32=mfma32 selects the "
@@ -458,13 +463,11 @@ def conv16(src, weight, cout, ksize, *, src1=None, gn=None, gn_silu=True, bias=N
     concat_c(src, src1) [B,Hs,Ws,Cin] fp16: raw with `gn` = (scale, shift) (3x3 only: GroupNorm affine + swish fused,
     applied in LDS) or already activated.  Returns an `Act` whose tensor is fp16 [B,H,W,cout] and whose GroupNorm
     partials (when the launch can emit them) describe exactly those rounded values."""
-    src = src.t if isinstance(src, Act) else src
-    src1 = src1.t if isinstance(src1, Act) else src1
-    res = res.t if isinstance(res, Act) else res
+    src, src1, res = tensor_of(src), tensor_of(src1), tensor_of(res)
     B, Hs, Ws, _ = src.shape
     H, W = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
     if skip is not None:
-        skip = tuple(None if s is None else (s.t if isinstance(s, Act) else s) for s in skip)
+        skip = tuple(tensor_of(s) for s in skip)
     d = _conv16_desc(src, weight, cout, ksize, H, W, ups, skip, skip_weight, bias, res, res_ups, src1, gn, gn_silu)
     L = _lib.lib()
     if out is None:
@@ -496,45 +499,30 @@ def conv16(src, weight, cout, ksize, *, src1=None, gn=None, gn_silu=True, bias=N
     if need > 0:
         ws = _conv_workspace(src.device, need)
         d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
-    if _timer is None:
-        check(L.ddnm_conv16(ctypes.byref(d), _stream()), "ddnm_conv16")
-    else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(L.ddnm_conv16(ctypes.byref(d), _stream()), "ddnm_conv16")
-        e1.record()
-        flops = 2.0 * B * H * W * cout * (ksize * ksize * d.Cin + d.SC0 + d.SC1)
-        _timer.records.append((f"conv16<{ksize}x{ksize}>", flops, e0, e1))
-        _timer.shapes.append((B, H, W, d.Cin, cout, ksize, 1, int(ups), d.SC0 + d.SC1, False, res is not None))
+    _launch(L.ddnm_conv16, d, "ddnm_conv16",
+            lambda: (f"conv16<{ksize}x{ksize}>", 2.0 * B * H * W * cout * (ksize * ksize * d.Cin + d.SC0 + d.SC1),
+                     (B, H, W, d.Cin, cout, ksize, 1, int(ups), d.SC0 + d.SC1, False, res is not None)))
     return Act(out, stats, tiles, gn=(fin[6].scale, fin[6].shift, fin[0], fin[6], fin[6].generation) if fused_fin else None)
 
 
 def conv16_out(src, weight, cout, bias=None, gn=None, gn_silu=True):
     """The network's output convolution on the fp16 path: 3x3, cout <= 32, fp32 NCHW result (unet.py:627-631,664);
     `gn` = (scale, shift) fuses the GroupNorm affine + swish of `out.0/out.1` into its loader like `conv16`."""
-    src = src.t if isinstance(src, Act) else src
+    src = tensor_of(src)
     B, H, W, _ = src.shape
     d = _conv16_desc(src, weight, cout, 3, H, W, False, None, None, bias, None, False, None, gn, gn_silu)
     d.out_nchw_f32 = 1
     out = torch.empty(B, cout, H, W, dtype=torch.float32, device=src.device)
     d.out = out.data_ptr()
-    if _timer is None:
-        check(_lib.lib().ddnm_conv16(ctypes.byref(d), _stream()), "ddnm_conv16(out)")
-    else:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_lib.lib().ddnm_conv16(ctypes.byref(d), _stream()), "ddnm_conv16(out)")
-        e1.record()
-        _timer.records.append(("conv16<out>", 2.0 * B * H * W * cout * 9 * d.Cin, e0, e1))
-        _timer.shapes.append((B, H, W, d.Cin, cout, 3, 1, 0, 0, False, False))
+    _launch(_lib.lib().ddnm_conv16, d, "ddnm_conv16(out)",
+            lambda: ("conv16<out>", 2.0 * B * H * W * cout * 9 * d.Cin, (B, H, W, d.Cin, cout, 3, 1, 0, 0, False, False)))
     return out
 
 
 def gn_apply16(src0, src1, gn, silu, pool=False):
     """fp16 operand of the next convolution: act(concat_c(src0, src1) * scale + shift), optionally 2x2 average-pooled
     (gn=None: plain concat / pooling of the raw tensors)."""
-    src0 = src0.t if isinstance(src0, Act) else src0
-    src1 = src1.t if isinstance(src1, Act) else src1
+    src0, src1 = tensor_of(src0), tensor_of(src1)
     B, H, W, C0 = src0.shape
     C1 = 0 if src1 is None else src1.shape[3]
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
@@ -546,8 +534,7 @@ def gn_apply16(src0, src1, gn, silu, pool=False):
 
 
 def im2col16(src0, src1, gn, silu):
-    src0 = src0.t if isinstance(src0, Act) else src0
-    src1 = src1.t if isinstance(src1, Act) else src1
+    src0, src1 = tensor_of(src0), tensor_of(src1)
     B, H, W, C0 = src0.shape
     C1 = 0 if src1 is None else src1.shape[3]
     out = torch.empty(B, H, W, 9 * (C0 + C1), dtype=torch.float16, device=src0.device)
@@ -690,15 +677,9 @@ def bgemm(A, Bm, C, M, N, K, *, lda, ldb, ldc, transb, batch=1, inner=1, sA=(0, 
     d.transb, d.batch, d.inner = int(transb), batch, inner
     d.sAo, d.sAi, d.sBo, d.sBi, d.sCo, d.sCi, d.sDo, d.sDi = sA[0], sA[1], sB[0], sB[1], sC[0], sC[1], sD[0], sD[1]
     d.alpha, d.beta, d.transa = alpha, beta, int(transa)
-    if _timer is not None:           # FLOP accounting of an instrumented pass (bench.py counts the classifier's work)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_lib.lib().ddnm_bgemm_f32(ctypes.byref(d), _stream()), "ddnm_bgemm_f32")
-        e1.record()
-        _timer.records.append(("bgemm_f32", 2.0 * M * N * K * batch, e0, e1))
-        _timer.shapes.append((batch, M, N, K, 0, 1, 1, 0, 0, False, False))
-        return C
-    check(_lib.lib().ddnm_bgemm_f32(ctypes.byref(d), _stream()), "ddnm_bgemm_f32")
+    # (timed too: FLOP accounting of an instrumented pass -- bench.py counts the classifier's work)
+    _launch(_lib.lib().ddnm_bgemm_f32, d, "ddnm_bgemm_f32",
+            lambda: ("bgemm_f32", 2.0 * M * N * K * batch, (batch, M, N, K, 0, 1, 1, 0, 0, False, False)))
     return C
 
 
