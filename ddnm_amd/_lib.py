@@ -210,6 +210,10 @@ PROTOTYPES = {
                                             c_int32, c_int32, POINTER(c_float), POINTER(StepScalars), c_void_p]),
     "ddnm_step_inpaint_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
                                               c_void_p, c_void_p, c_int32, c_int32, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_inpaint_pi_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
+                                           c_void_p, c_void_p, c_int32, c_int32, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_inpaint_pi_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int32,
+                                                 c_void_p, c_void_p, c_int32, c_int32, POINTER(StepScalars), c_void_p]),
     "ddnm_step_denoise_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_int32, c_int64, POINTER(StepScalars), c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
@@ -219,6 +223,8 @@ PROTOTYPES = {
     "ddnm_op_color_pinv_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, POINTER(c_float), c_void_p]),
     "ddnm_op_inpaint_A_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "ddnm_op_inpaint_pinv_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
+    "ddnm_op_inpaint_A_pi_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
+    "ddnm_op_inpaint_pinv_pi_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p]),
     "ddnm_fwht2d_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "ddnm_fwht2d_masked_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                                          c_void_p]),

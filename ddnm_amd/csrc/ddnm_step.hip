@@ -220,20 +220,23 @@ extern "C" int ddnm_step_color_f32(const float* xt, const float* et, int64_t et_
 }
 
 // ---------------------------------------------------------------- fused: inpainting (mask as rank table)
+// image b reads the rank table at rank + b * rank_bstride and its measurement row at y + b * y_bstride: (0, 3 * n_kept)
+// is one mask shared by the batch, (HW, y_stride) one mask per image (the *_pi_* entry points; rows padded to y_stride)
 template <class NZ>
 __global__ __launch_bounds__(256) void step_inpaint_kernel(const float* __restrict__ xt, const float* __restrict__ et,
                                                            int64_t et_bstride, NZ noise,
-                                                           const float* __restrict__ y, const int* __restrict__ rank,
-                                                           int n_kept, float* __restrict__ x0o,
+                                                           const float* __restrict__ y, int64_t y_bstride,
+                                                           const int* __restrict__ rank, int64_t rank_bstride,
+                                                           float* __restrict__ x0o,
                                                            float* __restrict__ xn, int64_t hw4, int64_t total4,
                                                            ddnm_step_scalars s) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / hw4, p = i - b * hw4;
         const auto nz = bind(noise, b);
         const int64_t base = (b * 3 * hw4 + p) * 4, ebase = b * et_bstride + p * 4;
-        const int4 rk = *reinterpret_cast<const int4*>(rank + p * 4);
+        const int4 rk = *reinterpret_cast<const int4*>(rank + b * rank_bstride + p * 4);
         const int rks[4] = {rk.x, rk.y, rk.z, rk.w};
-        const float* yb = y + b * (int64_t)3 * n_kept;
+        const float* yb = y + b * y_bstride;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const f32x4 e = ld4(et + ebase + c * hw4 * 4);
@@ -255,7 +258,42 @@ extern "C" int ddnm_step_inpaint_f32(const float* xt, const float* et, int64_t e
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * HW / 4;
     DDNM_LAUNCH(step_inpaint_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                       noise_src(noise, s, (int64_t)3 * HW), y, rank, n_kept, x0, xt_next, (int64_t)HW / 4, total4, *s);
+                       noise_src(noise, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0, xt_next, (int64_t)HW / 4,
+                       total4, *s);
+    return 0;
+}
+
+// one mask per image: rank [B][HW], y [B][y_stride] (row b: 3 * n_kept[b] entries, then padding that is never read)
+static inline int inpaint_pi_args(int32_t n_kept_max, int64_t y_stride, int32_t HW) {
+    if ((HW & 3) || (y_stride & 3) || n_kept_max < 1 || y_stride < (int64_t)3 * n_kept_max) return DDNM_E_SHAPE;
+    return 0;
+}
+
+extern "C" int ddnm_step_inpaint_pi_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                        const float* y, int64_t y_stride, const int32_t* rank, int32_t n_kept_max,
+                                        float* x0, float* xt_next, int32_t B, int32_t HW, const ddnm_step_scalars* s,
+                                        void* stream) {
+    if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    if (et_bstride & 3) return DDNM_E_SHAPE;
+    if (int e = inpaint_pi_args(n_kept_max, y_stride, HW)) return e;
+    const int64_t total4 = (int64_t)B * HW / 4;
+    DDNM_LAUNCH(step_inpaint_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                noise_src(noise, s, (int64_t)3 * HW), y, y_stride, rank, (int64_t)HW, x0, xt_next, (int64_t)HW / 4, total4,
+                *s);
+    return 0;
+}
+
+extern "C" int ddnm_step_inpaint_pi_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                              const float* y, int64_t y_stride, const int32_t* rank, int32_t n_kept_max,
+                                              float* x0, float* xt_next, int32_t B, int32_t HW,
+                                              const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
+    if (et_bstride & 3) return DDNM_E_SHAPE;
+    if (int e = inpaint_pi_args(n_kept_max, y_stride, HW)) return e;
+    const int64_t total4 = (int64_t)B * HW / 4;
+    DDNM_LAUNCH(step_inpaint_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                keyed_src(keys, s, (int64_t)3 * HW), y, y_stride, rank, (int64_t)HW, x0, xt_next, (int64_t)HW / 4, total4,
+                *s);
     return 0;
 }
 
@@ -329,7 +367,8 @@ extern "C" int ddnm_step_inpaint_keyed_f32(const float* xt, const float* et, int
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * HW / 4;
     DDNM_LAUNCH(step_inpaint_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                keyed_src(keys, s, (int64_t)3 * HW), y, rank, n_kept, x0, xt_next, (int64_t)HW / 4, total4, *s);
+                keyed_src(keys, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0, xt_next, (int64_t)HW / 4,
+                total4, *s);
     return 0;
 }
 
@@ -507,15 +546,18 @@ extern "C" int ddnm_op_color_pinv_f32(const float* y, float* x, int32_t B, int32
     return 0;
 }
 
-// y[b][3*rank[p] + c] = x[b][c][p] for kept pixels (HWC-interleaved measurement vector)
+// y[b][3*rank[b][p] + c] = x[b][c][p] for kept pixels (HWC-interleaved measurement vector); image b's table is at
+// rank + b * rank_bstride and its row at y + b * y_bstride (shared mask: (0, 3 * n_kept); per image: (HW, y_stride),
+// whose padding beyond 3 * n_kept[b] is the caller's to clear)
 __global__ __launch_bounds__(256) void inpaint_A_kernel(const float* __restrict__ x, const int* __restrict__ rank,
-                                                        int n_kept, float* __restrict__ y, int64_t HW, int64_t total) {
+                                                        int64_t rank_bstride, float* __restrict__ y, int64_t y_bstride,
+                                                        int64_t HW, int64_t total) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / HW, p = i - b * HW;
-        const int rk = rank[p];
+        const int rk = rank[b * rank_bstride + p];
         if (rk < 0) continue;
         const float* s = x + b * 3 * HW + p;
-        float* d = y + (b * n_kept + rk) * 3;
+        float* d = y + b * y_bstride + (int64_t)rk * 3;
         d[0] = s[0];
         d[1] = s[HW];
         d[2] = s[2 * HW];
@@ -526,22 +568,32 @@ extern "C" int ddnm_op_inpaint_A_f32(const float* x, const int32_t* rank, int32_
                                      int32_t HW, void* stream) {
     if (!x || !y || !rank || B <= 0 || HW <= 0) return DDNM_E_BADARG;
     const int64_t total = (int64_t)B * HW;
-    DDNM_LAUNCH(inpaint_A_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, x, rank, n_kept, y,
-                       (int64_t)HW, total);
+    DDNM_LAUNCH(inpaint_A_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, x, rank, (int64_t)0, y,
+                (int64_t)3 * n_kept, (int64_t)HW, total);
     return 0;
 }
 
-__global__ __launch_bounds__(256) void inpaint_pinv_kernel(const float* __restrict__ y, const int* __restrict__ rank,
-                                                           int n_kept, float* __restrict__ x, int64_t HW,
-                                                           int64_t total) {
+extern "C" int ddnm_op_inpaint_A_pi_f32(const float* x, const int32_t* rank, int32_t n_kept_max, float* y,
+                                        int64_t y_stride, int32_t B, int32_t HW, void* stream) {
+    if (!x || !y || !rank || B <= 0 || HW <= 0) return DDNM_E_BADARG;
+    if (int e = inpaint_pi_args(n_kept_max, y_stride, HW)) return e;
+    const int64_t total = (int64_t)B * HW;
+    DDNM_LAUNCH(inpaint_A_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, x, rank, (int64_t)HW, y, y_stride,
+                (int64_t)HW, total);
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void inpaint_pinv_kernel(const float* __restrict__ y, int64_t y_bstride,
+                                                           const int* __restrict__ rank, int64_t rank_bstride,
+                                                           float* __restrict__ x, int64_t HW, int64_t total) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t b = i / HW, p = i - b * HW;
-        const int rk = rank[p];
+        const int rk = rank[b * rank_bstride + p];
         float* d = x + b * 3 * HW + p;
         if (rk < 0) {
             d[0] = 0.f; d[HW] = 0.f; d[2 * HW] = 0.f;
         } else {
-            const float* s = y + (b * n_kept + rk) * 3;
+            const float* s = y + b * y_bstride + (int64_t)rk * 3;
             d[0] = s[0]; d[HW] = s[1]; d[2 * HW] = s[2];
         }
     }
@@ -551,8 +603,18 @@ extern "C" int ddnm_op_inpaint_pinv_f32(const float* y, const int32_t* rank, int
                                         int32_t HW, void* stream) {
     if (!x || !y || !rank || B <= 0 || HW <= 0) return DDNM_E_BADARG;
     const int64_t total = (int64_t)B * HW;
-    DDNM_LAUNCH(inpaint_pinv_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, y, rank, n_kept, x,
-                       (int64_t)HW, total);
+    DDNM_LAUNCH(inpaint_pinv_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, y, (int64_t)3 * n_kept, rank,
+                (int64_t)0, x, (int64_t)HW, total);
+    return 0;
+}
+
+extern "C" int ddnm_op_inpaint_pinv_pi_f32(const float* y, int64_t y_stride, const int32_t* rank, int32_t n_kept_max,
+                                           float* x, int32_t B, int32_t HW, void* stream) {
+    if (!x || !y || !rank || B <= 0 || HW <= 0) return DDNM_E_BADARG;
+    if (int e = inpaint_pi_args(n_kept_max, y_stride, HW)) return e;
+    const int64_t total = (int64_t)B * HW;
+    DDNM_LAUNCH(inpaint_pinv_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, y, y_stride, rank, (int64_t)HW, x,
+                (int64_t)HW, total);
     return 0;
 }
 

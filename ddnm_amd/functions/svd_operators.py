@@ -11,6 +11,8 @@ as one (or a few) hand-written HIP kernels:
   SRConv           -> Ae X Ae^T / Pe Y Pe^T on MFMA f32          (svd_operators.py:851-931)
   Colorization     -> w . rgb / w |w|^-2                         (svd_operators.py:627-667)
   Inpainting       -> gather / scatter through a rank table      (svd_operators.py:324-359)
+  InpaintingBank / PerImageInpainting -> the same with one mask (rank table) per image of the batch; the reference
+                      holds one mask per run, so each image is checked against its single-mask operator
   WalshHadamardCS  -> separable FWHT (shuffle + LDS) + permuted mask (svd_operators.py:211-251)
   Denoising        -> identity                                   (svd_operators.py:442-462)
 
@@ -409,6 +411,13 @@ class Colorization(A_functions):
                                       ctypes.byref(s), ops._stream()), fn)
 
 
+def _rank_table(keep):
+    """bool [HW] (pixel kept) -> int32 [HW]: index of the pixel among the kept ones in ascending order, -1 = missing."""
+    rank = torch.cumsum(keep.int(), 0) - 1
+    rank[~keep] = -1
+    return rank.to(torch.int32)
+
+
 class Inpainting(A_functions):
     def __init__(self, channels, img_dim, missing_indices, device):
         if channels != 3:
@@ -423,10 +432,8 @@ class Inpainting(A_functions):
         if not bool((miss.all(1) == miss.any(1)).all()):
             raise NotImplementedError("per-channel masks are not supported (reference masks whole pixels)")
         keep = ~miss[:, 0]
-        rank = torch.cumsum(keep.int(), 0) - 1
-        rank[~keep] = -1
         self.n_kept = int(keep.sum())
-        self.rank = rank.to(torch.int32).to(device).contiguous()
+        self.rank = _rank_table(keep).to(device).contiguous()
         self.kept_mask = keep.float().to(device).contiguous()            # [HW], shared by the 3 channel planes
         self.missing_indices = missing_indices
 
@@ -491,6 +498,129 @@ class Inpainting(A_functions):
         fn, nz = ops.step_noise_args("ddnm_step_inpaint_f32", noise, xt)
         check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(self.rank), self.n_kept, _p(x0_out), _p(xt_next), B,
                                       self.img_dim ** 2, ctypes.byref(s), ops._stream()), fn)
+
+
+class InpaintingBank:
+    """N inpainting masks for a run whose images each have their own hole: `masks` is [N, S, S] or [N, S*S], nonzero =
+    kept (the reference's `mask == 0 -> missing`, guided_diffusion/diffusion.py:465-470).  All N rank tables are built
+    once, like Inpainting's; `for_images(indices)` gives the operator of a batch, image i using mask i % N.  `y_dim`, the
+    row length of every measurement, is 3 * max(n_kept) rounded up to a multiple of 4 and constant for the bank, so
+    measurements of different loader batches concatenate."""
+
+    def __init__(self, channels, img_dim, masks, device):
+        if channels != 3:
+            raise ValueError(f"inpainting masks whole RGB pixels: channels must be 3, got {channels}")
+        masks = torch.as_tensor(np.asarray(masks))
+        hw = img_dim ** 2
+        if masks.dim() not in (2, 3) or masks.shape[0] < 1 or masks.numel() != masks.shape[0] * hw or \
+                (masks.dim() == 3 and tuple(masks.shape[1:]) != (img_dim, img_dim)):
+            raise ValueError(f"mask bank must be [N, {img_dim}, {img_dim}] or [N, {hw}], got {tuple(masks.shape)}")
+        keep = masks.reshape(masks.shape[0], hw) != 0
+        self.n_kept = [int(k) for k in keep.sum(1)]
+        if min(self.n_kept) < 1:
+            raise ValueError(f"mask {self.n_kept.index(min(self.n_kept))} of the bank keeps no pixel")
+        self.channels, self.img_dim, self.device = channels, img_dim, device
+        self.y_dim = 4 * ((3 * max(self.n_kept) + 3) // 4)
+        self.rank = torch.stack([_rank_table(k) for k in keep]).to(device).contiguous()      # [N][HW]
+        self.kept_mask = keep.float().to(device).contiguous()                                # [N][HW]
+
+    def __len__(self):
+        return len(self.n_kept)
+
+    def for_images(self, indices):
+        """The operator of the images with these global indices, in this order (one index-to-row gather on the device)."""
+        rows = [int(i) % len(self) for i in indices]
+        if not rows:
+            raise ValueError("for_images needs at least one image index")
+        idx = torch.tensor(rows, dtype=torch.long).to(self.device)
+        hw = self.img_dim ** 2
+        kept3 = self.kept_mask.index_select(0, idx)[:, None, :].expand(len(rows), 3, hw).contiguous()
+        return PerImageInpainting(self.img_dim, self.rank.index_select(0, idx), kept3, [self.n_kept[r] for r in rows],
+                                  self.y_dim, rows)
+
+
+class PerImageInpainting(A_functions):
+    """Inpainting whose mask differs per image: image b of the batch has the rank table `rank[b]` and the measurement row
+    y[b] = its 3 * n_kept[b] kept entries in the reference's HWC order (svd_operators.py:324-359), zero padded to
+    `y_dim`.  Built by InpaintingBank.for_images; `narrow` / `concat` re-batch built operators without a host round trip.
+    The operator is tied to its batch: every method raises ValueError for another batch size."""
+
+    def __init__(self, img_dim, rank, kept3, n_kept, y_dim, rows):
+        self.channels, self.img_dim, self.device = 3, img_dim, rank.device
+        self.rank, self.kept3 = rank, kept3               # int32 [B][HW]; fp32 [B][3][HW] kept-mask of the CHW planes
+        self.n_kept, self.y_dim, self.rows = list(n_kept), y_dim, list(rows)
+
+    def __len__(self):
+        return len(self.n_kept)
+
+    def _check_batch(self, B):
+        if B != len(self):
+            raise ValueError(f"PerImageInpainting holds the masks of {len(self)} images, the batch has {B} images")
+
+    def narrow(self, lo, hi):
+        """The operator of images [lo, hi) of this batch (views of its device rows)."""
+        if not 0 <= lo < hi <= len(self):
+            raise ValueError(f"narrow({lo}, {hi}) of a batch of {len(self)} images")
+        return PerImageInpainting(self.img_dim, self.rank[lo:hi], self.kept3[lo:hi], self.n_kept[lo:hi], self.y_dim,
+                                  self.rows[lo:hi])
+
+    @classmethod
+    def concat(cls, parts):
+        """One operator for the images of several batches of the same bank, in order."""
+        parts = list(parts)
+        if len({(p.img_dim, p.y_dim) for p in parts}) != 1:
+            raise ValueError("concat needs operators of one bank")
+        if len(parts) == 1:
+            return parts[0]
+        return cls(parts[0].img_dim, torch.cat([p.rank for p in parts], 0), torch.cat([p.kept3 for p in parts], 0),
+                   [n for p in parts for n in p.n_kept], parts[0].y_dim, [r for p in parts for r in p.rows])
+
+    def A(self, vec):
+        x = _img(vec, 3, self.img_dim)
+        B = x.shape[0]
+        self._check_batch(B)
+        y = ops.fill_(torch.empty(B, self.y_dim, dtype=torch.float32, device=x.device))      # padding is exactly 0
+        check(_lib.lib().ddnm_op_inpaint_A_pi_f32(_p(x), _p(self.rank), max(self.n_kept), _p(y), self.y_dim, B,
+                                                  self.img_dim ** 2, ops._stream()), "ddnm_op_inpaint_A_pi_f32")
+        return y
+
+    def A_pinv(self, vec):
+        B = vec.shape[0]
+        self._check_batch(B)
+        y = vec.reshape(B, -1).float().contiguous()
+        if y.shape[1] != self.y_dim:
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, the bank's y_dim is {self.y_dim}")
+        x = torch.empty(B, 3 * self.img_dim ** 2, dtype=torch.float32, device=y.device)
+        check(_lib.lib().ddnm_op_inpaint_pinv_pi_f32(_p(y), self.y_dim, _p(self.rank), max(self.n_kept), _p(x), B,
+                                                     self.img_dim ** 2, ops._stream()), "ddnm_op_inpaint_pinv_pi_f32")
+        return x
+
+    def _ragged(self, *args, **kwargs):
+        raise NotImplementedError("the spectral dimension is ragged (3 * n_kept differs per image): PerImageInpainting "
+                                  "has A, A_pinv, Lambda, Lambda_noise and ddnm_step only")
+
+    singulars = V = Vt = U = Ut = add_zeros = At = A_pinv_eta = _ragged
+
+    def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # Inpainting.Lambda with image b's mask
+        self._check_batch(vec.shape[0])
+        lam = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)[0]
+        return _mask_mix(_flat(vec), None, self.kept3, 3 * len(self), self.img_dim ** 2, lam, 1.0)
+
+    def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):
+        self._check_batch(vec.shape[0])
+        _, d1m, d2m = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)
+        _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
+        return _mask_mix(_flat(vec), _flat(epsilon), self.kept3, 3 * len(self), self.img_dim ** 2, d1m, d1n, d2m, d2n)
+
+    def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
+        B = xt.shape[0]
+        self._check_batch(B)
+        if y.shape[0] != B or y.numel() != B * self.y_dim:
+            raise ValueError(f"y must be [{B}, {self.y_dim}], got {tuple(y.shape)}")
+        ep, es = ops._et_args(et)
+        fn, nz = ops.step_noise_args("ddnm_step_inpaint_pi_f32", noise, xt)
+        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), self.y_dim, _p(self.rank), max(self.n_kept), _p(x0_out),
+                                      _p(xt_next), B, self.img_dim ** 2, ctypes.byref(s), ops._stream()), fn)
 
 
 class WalshHadamardCS(A_functions):
@@ -994,7 +1124,12 @@ def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask
             perm = torch.randperm(d ** 2, device=device)     # global device RNG, diffusion.py:458
         return WalshHadamardCS(c, d, compress_by, perm, device)
     if deg == "inpainting":
-        mask = torch.from_numpy(np.load(mask_path)).reshape(-1)
+        mask = np.load(mask_path)
+        if mask.ndim == 3:           # [N, S, S]: one mask per image, image i uses mask i % N
+            return InpaintingBank(c, d, mask, device)
+        if mask.ndim != 2:
+            raise ValueError(f"{mask_path}: a mask file is 2-D (one mask) or 3-D (a bank of masks), got {mask.ndim}-D")
+        mask = torch.from_numpy(mask).reshape(-1)
         r = torch.nonzero(mask == 0).long().reshape(-1) * 3
         return Inpainting(c, d, torch.cat([r, r + 1, r + 2], dim=0), device)
     if deg == "denoising":

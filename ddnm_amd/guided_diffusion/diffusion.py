@@ -16,7 +16,10 @@ Deliberate differences at the boundary (not in the results):
     restored shards meet in ONE RCCL all_gather per batch; rank 0 writes the PNGs and reports the PSNR;
   * DDNM_FUSE_BATCHES=K (default 1) restores up to K consecutive loader batches of a rank in one sampler call, each image
     with the noise it gets alone (per-image Philox keys, ops.KeyedPhiloxNoise): the shipped configs' batch of one image
-    leaves most of the chip idle.  Files, PSNR lines and totals are those of the unfused run.
+    leaves most of the chip idle.  Files, PSNR lines and totals are those of the unfused run;
+  * `--deg inpainting` with a 3-D `exp/inp_masks/mask.npy` [N, S, S] restores every image with its own hole: the image
+    written as `{i}_0.png` uses mask i % N (`restored_images`), in every sharding and fusing mode.  The reference holds
+    one mask per run; a 2-D file behaves as there.
 """
 import os
 import random
@@ -28,8 +31,8 @@ import torch.utils.data as data
 from .. import dist as ddist
 from .. import ops
 from ..functions.svd_ddnm import _AlphaTable, ddnm_diffusion, ddnm_plus_diffusion, get_schedule_jump
-from ..functions.svd_operators import (Colorization, Denoising, Inpainting, SuperResolution, build_operator,
-                                      mask_color_sr)
+from ..functions.svd_operators import (Colorization, Denoising, Inpainting, InpaintingBank, PerImageInpainting,
+                                      SuperResolution, build_operator, mask_color_sr)
 from .models import Model
 
 
@@ -271,6 +274,23 @@ def fuse_groups(n_items, batch_size, rank, world, k):
     return [owned[i:i + step] for i in range(0, len(owned), step)]
 
 
+def restored_images(n_items, batch_size, rank, world, k, start=0):
+    """Global image indices -- the i of `{i}_0.png`, `start` = --subset_start -- that each sampler call of `rank` restores,
+    in call order: the whole batches of a fused group (one rank, deal mode) or this rank's slice [lo, hi) of one batch
+    (split mode); a call without images (fewer images than ranks) is left out.  With a mask bank of N masks image i is
+    restored with mask i % N, whichever call it lands in."""
+    split = world > 1 and batch_size >= world
+    calls = []
+    for group in fuse_groups(n_items, batch_size, rank, world, k):
+        idx = []
+        for _, first, b in group:
+            lo, hi = ddist.shard_range(b, rank, world) if split else (0, b)
+            idx += range(start + first + lo, start + first + hi)
+        if idx:
+            calls.append(idx)
+    return calls
+
+
 class Diffusion(object):
     def __init__(self, args, config, device=None):
         self.args, self.config = args, config
@@ -445,6 +465,11 @@ class Diffusion(object):
         group_ends = {g[-1][0] for g in fuse_groups(len(loader.dataset), config.sampling.batch_size, rank, world, K)} \
             if fuse else set()
         pending = []
+        # a mask bank (3-D mask.npy): every loader batch gets the operator of ITS images, image i using mask i % N; a
+        # sampler call's operator is a slice (split mode) or the concatenation (fused group) of those
+        bank = A_funcs if isinstance(A_funcs, InpaintingBank) else None
+        calls = iter(restored_images(len(loader.dataset), config.sampling.batch_size, rank, world, K if fuse else 1,
+                                     args.subset_start)) if bank is not None else None
 
         def finish(x_all, x_orig, idx0):
             nonlocal psnr_sum, n_done
@@ -456,7 +481,9 @@ class Diffusion(object):
             n_done += b
             print("PSNR: %.2f" % (psnr_sum / n_done))
 
-        def restore(x, y_loc, classes, noise):
+        def restore(x, y_loc, classes, noise, A_funcs):
+            if bank is not None and A_funcs.rows != [i % len(bank) for i in next(calls)]:
+                raise RuntimeError("sampler call and restored_images disagree about the images of this call")
             with torch.no_grad():
                 if sigma_y == 0.0:       # noise-free case, DDNM (diffusion.py:587-588)
                     xs, _ = ddnm_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, cls_fn=cls_fn,
@@ -483,6 +510,8 @@ class Diffusion(object):
             else:
                 noise = BatchNoise(args.seed, bi, b, (C, S, S), lo, hi, self.device)
                 x = noise.x_T()
+            if bank is not None:
+                A_funcs = bank.for_images(range(idx_so_far, idx_so_far + b))
             y = A_funcs.A(x_orig)                # the whole batch: operators are cheap, and the writer needs A^+ y of all
             if args.add_noise:
                 if philox:
@@ -504,14 +533,15 @@ class Diffusion(object):
                                os.path.join(args.image_folder, f"Apy/orig_{idx_so_far + i}.png"))
             if fuse:
                 # whole batches (lo, hi = 0, b): held until the last batch of the group, restored together
-                pending.append((x, y.reshape(b, -1).contiguous(), classes, noise, x_orig, idx_so_far))
+                pending.append((x, y.reshape(b, -1).contiguous(), classes, noise, x_orig, idx_so_far, A_funcs))
                 if bi in group_ends:
                     if philox:
                         fnoise = ops.KeyedPhiloxNoise.from_sources([(p[3], j) for p in pending for j in range(p[4].shape[0])])
                     else:
                         fnoise = FusedTape([p[3] for p in pending])
                     x_fused = restore(torch.cat([p[0] for p in pending], 0), torch.cat([p[1] for p in pending], 0),
-                                      torch.cat([p[2] for p in pending], 0), fnoise)
+                                      torch.cat([p[2] for p in pending], 0), fnoise,
+                                      A_funcs if bank is None else PerImageInpainting.concat([p[6] for p in pending]))
                     off = 0
                     for p in pending:                # one PSNR line per loader batch, in loader order
                         nb = p[4].shape[0]
@@ -521,7 +551,8 @@ class Diffusion(object):
                 idx_so_far += b
                 continue
             if hi > lo:
-                x_loc = restore(x, y.reshape(b, -1)[lo:hi].contiguous(), classes, noise)
+                x_loc = restore(x, y.reshape(b, -1)[lo:hi].contiguous(), classes, noise,
+                                A_funcs if bank is None else A_funcs.narrow(lo, hi))
             else:
                 x_loc = x                    # empty shard (fewer images than ranks): takes part in the gather only
             x_all = x_loc if deal else ddist.gather_images(x_loc, n_total=b)      # the path's single collective (one per batch)
@@ -547,7 +578,10 @@ class Diffusion(object):
         if args.deg == "sr_averagepooling":
             return SuperResolution(config.data.channels, d, round(args.deg_scale), dev)   # AdaptiveAvgPool2d / MeanUpsample
         if args.deg == "inpainting":
-            mask = torch.from_numpy(np.load("exp/inp_masks/mask.npy")).reshape(-1)      # A = Ap = z * mask
+            mask = np.load("exp/inp_masks/mask.npy")
+            if mask.ndim == 3:
+                raise ValueError("per-image mask banks need the SVD path")
+            mask = torch.from_numpy(mask).reshape(-1)                                   # A = Ap = z * mask
             r = torch.nonzero(mask == 0).long().reshape(-1) * 3
             return Inpainting(config.data.channels, d, torch.cat([r, r + 1, r + 2], 0), dev)
         if args.deg in ("mask_color_sr", "diy"):                                         # :260-290

@@ -28,7 +28,9 @@ extern "C" {
 #define DDNM_E_BADARG (-1)   /* null pointer / non-positive size / misaligned */
 #define DDNM_E_SHAPE (-2)    /* shape not supported by this kernel family */
 
-int ddnm_version(void);                 /* ABI version, currently 7 (bumped on every struct / prototype change) */
+int ddnm_version(void);                 /* ABI version, currently 7 (bumped on every struct / prototype change; the
+                                           per-image inpainting entry points *_pi_* were added under 7: new symbols
+                                           only, no struct and no existing prototype changed) */
 const char* ddnm_build_digest(void);    /* sha256 of the sources + flags this binary was built from (build.py) */
 int ddnm_sizeof(int which);             /* sizeof of 0: ddnm_conv_desc, 1: ddnm_gemm_desc, 2: ddnm_conv16_desc,
                                            3: ddnm_step_scalars as compiled into the binary (-1: unknown index) */
@@ -504,6 +506,19 @@ int ddnm_step_inpaint_f32(const float* xt, const float* et, int64_t et_bstride, 
 int ddnm_step_denoise_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
                           const float* y, float* x0, float* xt_next, int32_t B, int64_t chw,
                           const ddnm_step_scalars* s, void* stream);
+/* Inpainting with one mask PER IMAGE ("pi"; functions/svd_operators.py:324-359 and guided_diffusion/diffusion.py:463-471
+ * applied to each image with its own mask -- the reference holds one mask per run):
+ *   rank: int32 [B][HW], row b = image b's table (pixel -> index among ITS kept pixels, -1 = missing);
+ *   y:    fp32 [B][y_stride], row b holds 3*n_kept[b] HWC-interleaved entries, the rest is padding (never read);
+ *   n_kept_max: largest n_kept of the batch (validation only).
+ * DDNM_E_SHAPE unless HW % 4 == et_bstride % 4 == y_stride % 4 == 0, n_kept_max >= 1 and y_stride >= 3*n_kept_max.
+ * Same kernel as ddnm_step_inpaint_f32 / _keyed_f32 (which are its rank row stride 0, y row stride 3*n_kept case). */
+int ddnm_step_inpaint_pi_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                             int64_t y_stride, const int32_t* rank, int32_t n_kept_max, float* x0, float* xt_next,
+                             int32_t B, int32_t HW, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_inpaint_pi_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                   const float* y, int64_t y_stride, const int32_t* rank, int32_t n_kept_max, float* x0,
+                                   float* xt_next, int32_t B, int32_t HW, const ddnm_step_scalars* s, void* stream);
 /* time-travel re-noise: xt' = a*x0 + b*noise  (svd_ddnm.py:74) */
 int ddnm_renoise_f32(const float* x0, const float* noise, float* xt_next, int64_t n, float a, float b, void* stream);
 
@@ -556,6 +571,13 @@ int ddnm_op_inpaint_A_f32(const float* x, const int32_t* rank, int32_t n_kept, f
                           void* stream);
 int ddnm_op_inpaint_pinv_f32(const float* y, const int32_t* rank, int32_t n_kept, float* x, int32_t B,
                              int32_t HW, void* stream);
+/* A and A^+ of inpainting with one mask per image (functions/svd_operators.py:324-359, guided_diffusion/diffusion.py:463-471;
+ * layout and validation as ddnm_step_inpaint_pi_f32).  A writes the 3*n_kept[b] entries of row b only: the caller clears
+ * the padding; A^+ does not read it. */
+int ddnm_op_inpaint_A_pi_f32(const float* x, const int32_t* rank, int32_t n_kept_max, float* y, int64_t y_stride,
+                             int32_t B, int32_t HW, void* stream);
+int ddnm_op_inpaint_pinv_pi_f32(const float* y, int64_t y_stride, const int32_t* rank, int32_t n_kept_max, float* x,
+                                int32_t B, int32_t HW, void* stream);
 /* Orthonormal 2-D separable Walsh-Hadamard transform H_n (x) H_n of each [n][n] plane
  * (== the 1-D natural-order FWHT over n*n points of svd_operators.py:212-222), n in {32,...,256}.
  * mask (optional, [planes_mask][n*n], plane p uses mask[(p % planes_mask)]) multiplies the
