@@ -836,22 +836,31 @@ extern "C" int ddnm_site_matmul_f32(const float* in, const float* M, float* out,
 //   sigma_t < thr: lambda = s*sigma_t*sqrt(1-eta^2)/a/sigma_y, d = (sigma_t*eta, 0)
 //   sigma_t > thr: lambda = 1, d = (sqrt(sigma_t^2 - a^2 sigma_y^2 inv^2), 0)
 //   s == 0 (and a tie): lambda = 1, d = (sigma_t*eta, sigma_t*sqrt(1-eta^2));  a == 0 or sigma_y == 0: no regime change
+
+// (lambda, d1, d2) of one spectral entry with singular value s: the rule above, shared by spectral_mix_kernel and
+// step_plus_spectral_kernel (eta_c = sqrt(1 - eta^2), active = a != 0 && sigma_y != 0)
+struct SpectralCoef { float lam, d1, d2; };
+__device__ __forceinline__ SpectralCoef spectral_coef(float s, bool active, float a, float sy, float st, float eta,
+                                                      float eta_c) {
+    const float inv = s == 0.f ? 0.f : 1.f / s;
+    float lam = 1.f, d1 = st * eta, d2 = st * eta_c;
+    if (active) {
+        const float thr = a * sy * inv;
+        if (st < thr) { lam = s * st * eta_c / a / sy; d2 = 0.f; }
+        if (st > thr) { d1 = sqrtf(st * st - a * a * (sy * sy) * (inv * inv)); d2 = 0.f; }
+        if (s == 0.f) { d1 = st * eta; d2 = st * eta_c; }
+    }
+    return SpectralCoef{lam, d1, d2};
+}
+
 __global__ __launch_bounds__(256) void spectral_mix_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                            const float* __restrict__ stab, int64_t plane_elems,
                                                            float* __restrict__ out, int64_t total, float a, float sy,
                                                            float st, float eta, float eta_c, int mode) {
     const bool active = a != 0.f && sy != 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const float s = stab[i % plane_elems];
-        const float inv = s == 0.f ? 0.f : 1.f / s;
-        float lam = 1.f, d1 = st * eta, d2 = st * eta_c;
-        if (active) {
-            const float thr = a * sy * inv;
-            if (st < thr) { lam = s * st * eta_c / a / sy; d2 = 0.f; }
-            if (st > thr) { d1 = sqrtf(st * st - a * a * (sy * sy) * (inv * inv)); d2 = 0.f; }
-            if (s == 0.f) { d1 = st * eta; d2 = st * eta_c; }
-        }
-        out[i] = mode == 0 ? x[i] * lam : x[i] * d1 + y[i] * d2;
+        const SpectralCoef c = spectral_coef(stab[i % plane_elems], active, a, sy, st, eta, eta_c);
+        out[i] = mode == 0 ? x[i] * c.lam : x[i] * c.d1 + y[i] * c.d2;
     }
 }
 
@@ -863,6 +872,84 @@ extern "C" int ddnm_spectral_mix_f32(const float* x, const float* y, const float
     const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
     DDNM_LAUNCH(spectral_mix_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, x, y, singulars, plane_elems, out,
                 total, a, sigma_y, sigma_t, eta, eta_c, mode);
+    return 0;
+}
+
+// ---------------------------------------------------------------- fused DDNM+ step in the spectral planes
+// One DDNM+ reverse step (functions/svd_ddnm.py:118-131) of an operator with a separable SVD, A = Ul diag(g) Vl^T (.) Vr Ur^T
+// per plane (SRConv, Deblurring2D), collapsed in the planes x^ = Vl^T X Vr.  With x^_t, e^ the transformed x_t and eps,
+// y^ = g^+ .* (Ul^T Y Ur) (zero where g = 0), a = sqrt_at_next and n ~ N(0, I):
+//   x^_0 = (x^_t - e^ * sqrt(1 - abar_t)) / sqrt(abar_t)
+//   z^   = a * (x^_0 - mu .* (x^_0 - y^)) + d1 .* n + d2 .* e^            X_{t-1} = Vl z^ Vr^T
+// (lambda, d1, d2) = spectral_coef(g) per entry of the THRESHOLDED gain table; mu = lambda where g > 0, else 0 (null
+// space: no correction, (d1, d2) = (sigma_t eta, sigma_t sqrt(1 - eta^2))).  Unlike Lambda_noise of the reference's other
+// operators, eps enters as V^T eps; n is drawn directly in the spectral planes (V orthogonal: same distribution).
+// [B][C][plane] in one pass, float4 per lane: 3 reads + the cached table (gains + c * gains_cstride; stride 0 = one
+// table for all channels), 1 write.  out_hat may alias xt_hat: every lane reads its four entries before it stores them.
+template <class NZ>
+__global__ __launch_bounds__(256) void step_plus_spectral_kernel(const float* xt_hat, const float* __restrict__ et_hat,
+                                                                 const float* __restrict__ y_hat,
+                                                                 const float* __restrict__ gains, int64_t gains_cstride,
+                                                                 NZ noise, float* out_hat, int64_t plane4, int64_t chw4,
+                                                                 int64_t total4, ddnm_step_scalars s, float sy, float st,
+                                                                 float eta, float eta_c) {
+    const float a = s.sqrt_at_next;
+    const bool active = a != 0.f && sy != 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / chw4, r = i - b * chw4;
+        const int64_t c = r / plane4, p = r - c * plane4;
+        const auto nz = bind(noise, b);
+        const f32x4 e = ld4(et_hat + i * 4);
+        const f32x4 x0 = x0_of(ld4(xt_hat + i * 4), e, s);
+        const f32x4 yh = ld4(y_hat + i * 4);
+        const f32x4 g = ld4(gains + c * gains_cstride + p * 4);
+        const f32x4 n = nz4(nz, i * 4);
+        f32x4 mu, d1, d2;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const SpectralCoef k = spectral_coef(g[j], active, a, sy, st, eta, eta_c);
+            mu[j] = g[j] > 0.f ? k.lam : 0.f;
+            d1[j] = k.d1;
+            d2[j] = k.d2;
+        }
+        st4(out_hat + i * 4, ((x0 - (x0 - yh) * mu) * a + n * d1) + e * d2);
+    }
+}
+
+static inline int plus_spectral_args(const float* xt_hat, const float* et_hat, const float* y_hat, const float* gains,
+                                     int64_t gains_cstride, const float* out_hat, int32_t B, int32_t C, int64_t plane,
+                                     const ddnm_step_scalars* s) {
+    if (!xt_hat || !et_hat || !y_hat || !gains || !out_hat || !s || B <= 0 || C <= 0 || plane <= 0 || gains_cstride < 0)
+        return DDNM_E_BADARG;
+    if ((plane & 3) || (gains_cstride & 3)) return DDNM_E_SHAPE;
+    return 0;
+}
+
+extern "C" int ddnm_step_plus_spectral_f32(const float* xt_hat, const float* et_hat, const float* y_hat,
+                                           const float* gains, int64_t gains_cstride, const float* noise, float* out_hat,
+                                           int32_t B, int32_t C, int64_t plane, float sigma_y, float sigma_t, float eta,
+                                           const ddnm_step_scalars* s, void* stream) {
+    if (int e = plus_spectral_args(xt_hat, et_hat, y_hat, gains, gains_cstride, out_hat, B, C, plane, s)) return e;
+    if (!noise_ok(noise, s)) return DDNM_E_BADARG;
+    const int64_t chw = (int64_t)C * plane, total4 = (int64_t)B * chw / 4;
+    const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
+    DDNM_LAUNCH(step_plus_spectral_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt_hat, et_hat,
+                y_hat, gains, gains_cstride, noise_src(noise, s, chw), out_hat, plane / 4, chw / 4, total4, *s, sigma_y,
+                sigma_t, eta, eta_c);
+    return 0;
+}
+
+extern "C" int ddnm_step_plus_spectral_keyed_f32(const float* xt_hat, const float* et_hat, const float* y_hat,
+                                                 const float* gains, int64_t gains_cstride, const uint32_t* keys,
+                                                 float* out_hat, int32_t B, int32_t C, int64_t plane, float sigma_y,
+                                                 float sigma_t, float eta, const ddnm_step_scalars* s, void* stream) {
+    if (int e = plus_spectral_args(xt_hat, et_hat, y_hat, gains, gains_cstride, out_hat, B, C, plane, s)) return e;
+    if (!keys_ok(keys)) return DDNM_E_BADARG;
+    const int64_t chw = (int64_t)C * plane, total4 = (int64_t)B * chw / 4;
+    const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
+    DDNM_LAUNCH(step_plus_spectral_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt_hat,
+                et_hat, y_hat, gains, gains_cstride, keyed_src(keys, s, chw), out_hat, plane / 4, chw / 4, total4, *s,
+                sigma_y, sigma_t, eta, eta_c);
     return 0;
 }
 

@@ -356,7 +356,10 @@ def ddnm_plus_diffusion(x, model, b, eta, A_funcs, y, sigma_y, cls_fn=None, clas
       x_t-1 = sqrt(abar') x0^ + Lambda_noise( N(0,I), eps )                              (Eq. 51)
 
     with the operator's `Lambda` / `Lambda_noise` (spectral lambda_t and noise mixing).  Every product is a
-    HIP kernel; per step: UNet forward, x0 kernel, A / A^+ kernels, Lambda, Lambda_noise, combine."""
+    HIP kernel; per step: UNet forward, x0 kernel, A / A^+ kernels, Lambda, Lambda_noise, combine.  An operator with a
+    non-None `ddnm_plus_step` hook (SRConv, Deblurring2D: no Lambda in the reference) runs the whole operator part of the
+    step in its spectral planes instead: `begin_plus_run(y)` once, then x0 kernel, two two-sided GEMMs and one fused kernel
+    per step (svd_operators._SpectralPlus)."""
     if not x.is_cuda:
         raise RuntimeError("ddnm_amd.ddnm_plus_diffusion runs on the GPU only (no CPU fallback)")
     skip = config.diffusion.num_diffusion_timesteps // config.time_travel.T_sampling
@@ -368,6 +371,9 @@ def ddnm_plus_diffusion(x, model, b, eta, A_funcs, y, sigma_y, cls_fn=None, clas
     y = y.reshape(n, -1).float().contiguous()
     draw = _noise_source(noise, x)
     from .svd_operators import _axpby
+    plus_step = getattr(A_funcs, "ddnm_plus_step", None)     # SRConv / Deblurring2D: the step fused in the spectral planes
+    if plus_step is not None:
+        A_funcs.begin_plus_run(y)         # y^ of THIS call's measurement; never cached across runs
     xt = x
     x0_t = torch.empty_like(x)
     bufs = [torch.empty_like(x), torch.empty_like(x)]
@@ -393,17 +399,24 @@ def ddnm_plus_diffusion(x, model, b, eta, A_funcs, y, sigma_y, cls_fn=None, clas
                     cls = cls_const
                     eps = model(xt, t, cls)
                     et = _guided_eps(eps, guide.grad(i, t, cls), float((1 - at).sqrt()))
-                if et.size(1) == 6:
-                    et = et[:, :3].contiguous()
                 a, sigma_t = at_next.sqrt(), (1 - at_next).sqrt()
                 s = ops.step_scalars(at, at_next, eta)
-                ops.step_x0(xt, et, s, out=x0_t)
-                resid = _axpby(A_funcs.A(x0_t), y, 1.0, -1.0)
-                corr = A_funcs.Lambda(A_funcs.A_pinv(resid), a, sigma_y, sigma_t, eta).reshape(x.shape)
-                eps_k = draw(k) if draw.philox is None else draw.philox.tensor(k, x0_t)
-                nz = A_funcs.Lambda_noise(eps_k, a, sigma_y, sigma_t, eta, et).reshape(x.shape)
-                s.c1, s.c2, s.lam = 1.0, 0.0, 1.0        # x_t-1 = sqrt(abar') (x0 - corr) + 1 * nz
-                ops.step_combine(x0_t, corr, None, nz, et, s, out=out)
+                if plus_step is not None:
+                    if et.size(1) == 6:
+                        et = et[:, :3]               # read through its strides, no copy
+                    if draw.philox is not None:
+                        draw.philox.stamp(s, k)      # the step kernel draws its own noise (noise pointer NULL / key table)
+                    plus_step(xt, et, draw(k), s, sigma_y, float(sigma_t), eta, x0_t, out)
+                else:
+                    if et.size(1) == 6:
+                        et = et[:, :3].contiguous()
+                    ops.step_x0(xt, et, s, out=x0_t)
+                    resid = _axpby(A_funcs.A(x0_t), y, 1.0, -1.0)
+                    corr = A_funcs.Lambda(A_funcs.A_pinv(resid), a, sigma_y, sigma_t, eta).reshape(x.shape)
+                    eps_k = draw(k) if draw.philox is None else draw.philox.tensor(k, x0_t)
+                    nz = A_funcs.Lambda_noise(eps_k, a, sigma_y, sigma_t, eta, et).reshape(x.shape)
+                    s.c1, s.c2, s.lam = 1.0, 0.0, 1.0        # x_t-1 = sqrt(abar') (x0 - corr) + 1 * nz
+                    ops.step_combine(x0_t, corr, None, nz, et, s, out=out)
                 have_x0 = True
             else:
                 assert have_x0

@@ -24,8 +24,10 @@ kernel draws in-kernel from ddnm_step_scalars::rng_*) or an `ops.KeyedPhiloxNois
 
 `Lambda` / `Lambda_noise` (the sigma_y > 0 path of `ddnm_plus_diffusion`) follow the reference's
 per-class definitions, including its quirk of feeding the RAW patch / needle / permuted entries of
-the noise and of eps to `V` in `Lambda_noise`; `SRConv` has none and raises NotImplementedError
-like the reference.
+the noise and of eps to `V` in `Lambda_noise`.  `SRConv` and `Deblurring2D` define none, like the reference
+(`Lambda` raises NotImplementedError); their DDNM+ runs through the engine hook `ddnm_plus_step` instead
+(`_SpectralPlus`: the whole step fused in the operator's spectral planes, thresholded singular values, eps
+entering as V^T eps).  `Deblurring` opts out of the hook and keeps its `Lambda` / `Lambda_noise`.
 """
 import ctypes
 import os
@@ -890,7 +892,70 @@ class GeneralA(A_functions):
         return self.V(_gather(self.Ut(vec), None, self._d, scale=self._sinv_pad))
 
 
-class SRConv(A_functions):
+class _SpectralPlus:
+    """DDNM+ (sigma_y > 0) for operators whose SVD is separable per plane, A X = Ul (g .* (Vl^T X Vr)) Ur^T -- SRConv and
+    Deblurring2D.  The reference defines no Lambda / Lambda_noise for them (and neither do these classes: a flattened
+    spectral ordering would have to be invented); the whole step of functions/svd_ddnm.py:118-131 collapses in the planes
+    x^ = Vl^T X Vr instead (csrc/ddnm_step.hip, ddnm_step_plus_spectral_f32):
+
+      x^_0 = (x^_t - e^ sqrt(1 - abar_t)) / sqrt(abar_t),   z^ = a (x^_0 - mu .* (x^_0 - y^)) + d1 .* n + d2 .* e^,
+      X_{t-1} = Vl z^ Vr^T,   y^ = g^+ .* (Ul^T Y Ur)
+
+    with (lambda, d1, d2) = spectral_coefficients(g, ...) per entry of the THRESHOLDED gain table `g` (the values A and
+    A_pinv use; g = 0 is null space throughout: mu = 0, (d1, d2) = (sigma_t eta, sigma_t sqrt(1 - eta^2))) and mu = lambda
+    where g > 0.  eps enters as V^T eps -- the mathematically meant form, unlike the raw entries the reference's other
+    operators feed to V -- and n ~ N(0, I) is drawn directly in the spectral planes (V is orthogonal).
+    A subclass provides `_plus_factors()`; `ddnm_plus_diffusion` calls `begin_plus_run(y)` once and `ddnm_plus_step`
+    per reverse step."""
+
+    def _plus_factors(self):
+        """dict: Vl, Vlt, Vr, Vrt [d, d], Ult, Urt [m, m], m, gains / ginv [Cg][d*d] (Cg = 1 or channels)."""
+        raise NotImplementedError()
+
+    def begin_plus_run(self, y):
+        """Per-run constants: y^ (the measurement in the spectral planes, zero in the null space) and the scratch planes."""
+        f = self._plus_factors()
+        C, d, m = self.channels, self.img_dim, f["m"]
+        y = _flat(y)
+        B = y.shape[0]
+        if y.shape[1] != C * m * m:
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, expected {C} x {m} x {m}")
+        bc = B * C
+        t = torch.empty(bc, m, m, dtype=torch.float32, device=y.device)
+        ops.bgemm(f["Ult"], y, t, m, m, m, lda=m, ldb=m, ldc=m, transb=False, batch=bc, sB=(m * m, 0), sC=(m * m, 0))
+        y_hat = ops.fill_(torch.empty(B, C, d, d, dtype=torch.float32, device=y.device))
+        # (Ul^T Y) Ur into the top-left m x m of each zeroed d x d plane (ldc = d), then g^+
+        ops.bgemm(t, f["Urt"], y_hat, m, m, m, lda=m, ldb=m, ldc=d, transb=True, batch=bc, sA=(m * m, 0), sC=(d * d, 0))
+        check(_lib.lib().ddnm_mul_planes_f32(_p(y_hat), _p(f["ginv"]), f["ginv"].shape[0], d * d, _p(y_hat),
+                                             y_hat.numel(), ops._stream()), "ddnm_mul_planes_f32")
+        self._plus_run = (B, y_hat, torch.empty(2, bc, d, d, dtype=torch.float32, device=y.device),
+                          torch.empty(2, B, C, d, d, dtype=torch.float32, device=y.device))
+
+    def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
+        """One DDNM+ reverse step: x0|t into `x0_out` (uncorrected, as the loop returns and time-travels from it), x_{t-1}
+        into `xt_next`.  `et` may be the [:, :3] view of a 6-channel network output (read through its strides)."""
+        run = getattr(self, "_plus_run", None)
+        B = xt.shape[0]
+        if run is None or run[0] != B:
+            raise RuntimeError("ddnm_plus_step needs begin_plus_run(y) for this batch first")
+        _, y_hat, t1, hat = run
+        f = self._plus_factors()
+        C, d = self.channels, self.img_dim
+        bc, dd = B * C, d * d
+        ops.step_x0(xt, et, s, out=x0_out)                 # validates et's layout too
+        # x^_t = Vl^T X_t Vr and e^ = Vl^T E Vr: left products per tensor, the right product over all 2 B C planes
+        ops.bgemm(f["Vlt"], xt, t1[0], d, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, sB=(dd, 0), sC=(dd, 0))
+        ops.bgemm(f["Vlt"], et, t1[1], d, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, inner=C,
+                  sB=(et.stride(0), dd), sC=(C * dd, dd))
+        ops.bgemm(t1, f["Vrt"], hat, d, d, d, lda=d, ldb=d, ldc=d, transb=True, batch=2 * bc, sA=(dd, 0), sC=(dd, 0))
+        g = f["gains"]
+        ops.step_plus_spectral(hat[0], hat[1], y_hat, g, dd if g.shape[0] > 1 else 0, noise, s, sigma_y, sigma_t, eta,
+                               out=hat[0])
+        ops.bgemm(f["Vl"], hat[0], t1[0], d, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, sB=(dd, 0), sC=(dd, 0))
+        ops.bgemm(t1[0], f["Vr"], xt_next, d, d, d, lda=d, ldb=d, ldc=d, transb=True, batch=bc, sA=(dd, 0), sC=(dd, 0))
+
+
+class SRConv(_SpectralPlus, A_functions):
     ZERO = 3e-2     # svd_operators.py:878
 
     def __init__(self, kernel, channels, img_dim, device, stride=1):
@@ -996,6 +1061,19 @@ class SRConv(A_functions):
         ops.bgemm(t2, self.Pe, x, d, d, m, lda=m, ldb=m, ldc=d, transb=True, batch=bc, sA=(d * m, 0), sC=(d * d, 0))
         return x
 
+    def _plus_factors(self):
+        if not hasattr(self, "_plus_f"):
+            U, V = self._svd_host
+            dev, d, m = self.device, self.img_dim, self.small_dim
+            S = self.singulars_small.detach().cpu()
+            g = torch.zeros(d, d)
+            g[:m, :m] = S[:, None] * S[None, :]                          # thresholded: the values Ae / Pe are built from
+            dv = lambda t: t.contiguous().to(dev)                        # noqa: E731
+            self._plus_f = dict(Vl=dv(V), Vlt=dv(V.T), Vr=dv(V), Vrt=dv(V.T), Ult=dv(U.T), Urt=dv(U.T), m=m,
+                                gains=dv(g.reshape(1, d * d)),
+                                ginv=dv(torch.where(g > 0, 1.0 / g, torch.zeros_like(g)).reshape(1, d * d)))
+        return self._plus_f
+
     def singulars(self):
         s = self.singulars_small
         return torch.matmul(s.reshape(-1, 1), s.reshape(1, -1)).reshape(-1).repeat_interleave(3).reshape(-1)
@@ -1008,7 +1086,7 @@ class SRConv(A_functions):
         ops.step_combine(x0_out, proj, None, noise, et, s, out=xt_next)
 
 
-class Deblurring2D(A_functions):
+class Deblurring2D(_SpectralPlus, A_functions):
     """Separable blur A = (U1 (x) U2) diag(g) (V1 (x) V2)^T (svd_operators.py:1094-1165), applied as four
     N x N MFMA GEMMs per plane + one gain kernel.  The gain table reproduces the reference's tiling quirk
     (`singulars()` = sorted values repeated 3x against a (position, channel)-interleaved spectral vector):
@@ -1073,11 +1151,20 @@ class Deblurring2D(A_functions):
         y = _img(vec, self.channels, self.img_dim)
         return self._sandwich(self.U1t, y, self.U2t, self.Ginv, self.V1, self.V2)
 
+    def _plus_factors(self):
+        # the per-channel table self.G (thresholded, with the 3x tiling quirk): the values A / A_pinv use
+        return dict(Vl=self.V1, Vlt=self.V1t, Vr=self.V2, Vrt=self.V2t, Ult=self.U1t, Urt=self.U2t, m=self.img_dim,
+                    gains=self.G, ginv=self.Ginv)
+
     def singulars(self):
         return self._singulars.repeat(1, 3).reshape(-1)
 
 
 class Deblurring(Deblurring2D):
+    # deblur_uni / deblur_gauss keep the reference's Lambda / Lambda_noise (un-thresholded table, raw eps): no spectral hook
+    begin_plus_run = None
+    ddnm_plus_step = None
+
     def __init__(self, kernel, channels, img_dim, device, ZERO=3e-2):
         self.ZERO = ZERO
         super().__init__(kernel, kernel, channels, img_dim, device)

@@ -900,6 +900,27 @@ def step_combine(x0, proj, apy, noise, et, s, out=None):
     return out
 
 
+def step_plus_spectral(xt_hat, et_hat, y_hat, gains, gains_cstride, noise, s, sigma_y, sigma_t, eta, out=None):
+    """The fused DDNM+ step in the spectral planes (include/ddnm_hip.h::ddnm_step_plus_spectral_f32): `xt_hat`, `et_hat`,
+    `y_hat` are [B, C, d, d]; `gains` the thresholded gain table, [C][d*d] with channel stride `gains_cstride` (0: one
+    plane for all channels); `noise` a tensor, None (in-kernel draw per ddnm_step_scalars::rng_*) or a KeyedPhiloxNoise.
+    `out` may be `xt_hat`."""
+    B, C = xt_hat.shape[0], xt_hat.shape[1]
+    plane = xt_hat.numel() // (B * C)
+    out = torch.empty_like(xt_hat) if out is None else out
+    for name, t in (("xt_hat", xt_hat), ("et_hat", et_hat), ("y_hat", y_hat), ("out", out)):
+        if _f32c(t, name).numel() != B * C * plane:
+            raise ValueError(f"step_plus_spectral: {name} has {t.numel()} entries, expected {B * C * plane}")
+    if _f32c(gains, "gains").numel() < (C - 1) * gains_cstride + plane:
+        raise ValueError("step_plus_spectral: the gain table is shorter than (C - 1) * gains_cstride + plane")
+    if noise is not None and not isinstance(noise, KeyedPhiloxNoise) and _f32c(noise, "noise").numel() != B * C * plane:
+        raise ValueError("step_plus_spectral: the noise tensor must have one entry per spectral entry")
+    fn, nz = step_noise_args("ddnm_step_plus_spectral_f32", noise, xt_hat)
+    check(getattr(_lib.lib(), fn)(_p(xt_hat), _p(et_hat), _p(y_hat), _p(gains), gains_cstride, nz, _p(out), B, C, plane,
+                                  float(sigma_y), float(sigma_t), float(eta), ctypes.byref(s), _stream()), fn)
+    return out
+
+
 def fill_(t, value=0.0):
     """t[...] = value for a contiguous fp32 tensor (or contiguous slice) through ddnm_fill_f32."""
     if t.numel():

@@ -562,6 +562,25 @@ int ddnm_mul_planes_f32(const float* x, const float* table, int32_t planes_table
 int ddnm_spectral_mix_f32(const float* x, const float* y, const float* singulars, int64_t plane_elems, float* out,
                           int64_t total, float a, float sigma_y, float sigma_t, float eta, int32_t mode, void* stream);
 
+/* One fused DDNM+ step (svd_ddnm.py:118-131) in the spectral planes x^ = Vl^T X Vr of an operator with a separable SVD
+ * (SRConv, Deblurring2D), all tensors [B][C][plane] contiguous:
+ *   x^_0 = (xt_hat - et_hat * sqrt_1m_at) / sqrt_at
+ *   out_hat = a * (x^_0 - mu .* (x^_0 - y_hat)) + d1 .* n + d2 .* et_hat,   a = s->sqrt_at_next, n ~ N(0, I)
+ * (lambda, d1, d2) per entry of the THRESHOLDED gain table by the rule of ddnm_spectral_mix_f32, mu = lambda where the
+ * gain is > 0 and 0 in the null space; y_hat = g^+ .* (Ul^T Y Ur), zero where g = 0.  gains [C][plane] with channel
+ * stride gains_cstride (0: one table for all channels).  noise: a tensor [B][C*plane], or NULL with s->rng_on (drawn
+ * in-kernel, counter (r / 4, rng_iter, rng_image_base + b, 0), r = index inside the image: the values of
+ * ddnm_randn_philox_f32 on [B][C*plane]); the keyed form takes the per-image key table instead.  out_hat may alias
+ * xt_hat.  plane % 4 != 0 or gains_cstride % 4 != 0: DDNM_E_SHAPE. */
+int ddnm_step_plus_spectral_f32(const float* xt_hat, const float* et_hat, const float* y_hat, const float* gains,
+                                int64_t gains_cstride, const float* noise, float* out_hat, int32_t B, int32_t C,
+                                int64_t plane, float sigma_y, float sigma_t, float eta, const ddnm_step_scalars* s,
+                                void* stream);
+int ddnm_step_plus_spectral_keyed_f32(const float* xt_hat, const float* et_hat, const float* y_hat, const float* gains,
+                                      int64_t gains_cstride, const uint32_t* rng_keys, float* out_hat, int32_t B,
+                                      int32_t C, int64_t plane, float sigma_y, float sigma_t, float eta,
+                                      const ddnm_step_scalars* s, void* stream);
+
 /* Stand-alone operator kernels (A and A^+ of functions/svd_operators.py, direct form). */
 int ddnm_op_avgpool_f32(const float* x, float* y, int32_t BC, int32_t H, int32_t W, int32_t r, void* stream);
 int ddnm_op_upsample_f32(const float* y, float* x, int32_t BC, int32_t H, int32_t W, int32_t r, void* stream);
