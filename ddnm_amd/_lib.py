@@ -221,6 +221,13 @@ PROTOTYPES = {
     "ddnm_step_plus_spectral_keyed_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                                     c_int32, c_int32, c_int64, c_float, c_float, c_float,
                                                     POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_cs_pre_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float,
+                                            c_float, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_cs_pre_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+                                                  c_float, c_float, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_cs_post_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ddnm_op_avgpool_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_op_upsample_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

@@ -1002,6 +1002,112 @@ extern "C" int ddnm_patchify_f32(const float* src, float* dst, int32_t planes, i
     return 0;
 }
 
+// ---------------------------------------------------------------- fused DDNM+ step of block-based CS, per patch
+// One DDNM+ reverse step (functions/svd_ddnm.py:118-131) of CS (svd_operators.py:101-159).  Every singular value is 1
+// (:110), so the spectral coefficients take two values per step -- (lambda, d1r, d2r) on the measured subspace, (1, d1n,
+// d2n) on the null space -- and with M = Vt_small[:cs] (orthonormal rows, M^T M the projector onto the measured subspace
+// of a patch), a = sqrt_at_next and n ~ N(0, I) drawn in the image domain the step is
+//   x0      = (x_t - eps * sqrt_1m_at) / sqrt_at
+//   w       = -a lambda x0 + (d1r - d1n) n + (d2r - d2n) eps                    patch layout [patches][ps*ps]
+//   x_{t-1} = a x0 + d1n n + d2n eps + a lambda A^+ y + unpatch((w M^T) M)
+// = a (x0 - Lambda A^+ (A x0 - y)) + V (d1 .* V^T n + d2 .* V^T eps) without the full V_small.  The pre kernel writes x0,
+// the image-order part of x_{t-1} and w; two ddnm_bgemm_f32 launches (the products of CS.A / CS.A_pinv) project w; the
+// post kernel adds the projection.  The five coefficients come from the host (svd_operators.cs_plus_coefficients).
+struct CsPlusCoef { float al, d1n, d2n, dd1, dd2; };   // a*lambda, d1n, d2n, d1r - d1n, d2r - d2n
+
+// one float4 per lane in image order [B][C][D][D]: 3 reads (+ the noise tensor), 3 writes; four consecutive pixels of a
+// row stay inside one patch row (ps % 4 == 0), so the store into w is one 16-byte piece at patchify_kernel's position
+template <class NZ>
+__global__ __launch_bounds__(256) void cs_plus_pre_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                          int64_t et_bstride, NZ noise, const float* __restrict__ aty,
+                                                          float* __restrict__ x0o, float* __restrict__ xn,
+                                                          float* __restrict__ w, int C, int D, int ps, int64_t chw4,
+                                                          int64_t total4, ddnm_step_scalars s, CsPlusCoef k) {
+    const int npd = D / ps, D4 = D >> 2;
+    const float a = s.sqrt_at_next;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / chw4, r = i - b * chw4;
+        const auto nz = bind(noise, b);
+        const f32x4 e = ld4(et + b * et_bstride + r * 4);
+        const f32x4 x0 = x0_of(ld4(xt + i * 4), e, s);
+        const f32x4 ay = ld4(aty + i * 4);
+        const f32x4 n = nz4(nz, i * 4);
+        st4(x0o + i * 4, x0);
+        st4(xn + i * 4, ((x0 * a + n * k.d1n) + e * k.d2n) + ay * k.al);
+        // r = (c*D + yy)*D4 + x4 inside the image -> row (plane, py, px), column rr*ps + xx%ps of the patch matrix
+        int64_t t = r;
+        const int x4 = (int)(t % D4); t /= D4;
+        const int yy = (int)(t % D);
+        const int64_t plane = b * C + t / D;
+        const int xx = x4 * 4, py = yy / ps, px = xx / ps;
+        const int64_t pos = ((((plane * npd + py) * npd + px) * ps + (yy - py * ps)) * ps) + (xx - px * ps);
+        st4(w + pos, (n * k.dd1 + e * k.dd2) - x0 * k.al);
+    }
+}
+
+static inline int plus_cs_pre_args(const float* xt, const float* et, int64_t et_bstride, const float* aty,
+                                   const float* x0_out, const float* xt_next, const float* w, int32_t B, int32_t C,
+                                   int32_t D, int32_t ps, const ddnm_step_scalars* s) {
+    if (!xt || !et || !aty || !x0_out || !xt_next || !w || !s || B <= 0 || C <= 0 || D <= 0 || ps <= 0)
+        return DDNM_E_BADARG;
+    if (D % ps || ps % 4 || (et_bstride & 3)) return DDNM_E_SHAPE;
+    if (xt_next == xt || xt_next == et || xt_next == x0_out || w == xt || w == et || w == aty || w == x0_out ||
+        w == xt_next || x0_out == xt || x0_out == et || x0_out == aty || xt_next == aty)
+        return DDNM_E_BADARG;
+    return 0;
+}
+
+extern "C" int ddnm_step_plus_cs_pre_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                         const float* aty, float* x0_out, float* xt_next, float* w, int32_t B, int32_t C,
+                                         int32_t D, int32_t ps, float a_lambda, float d1n, float d2n, float dd1,
+                                         float dd2, const ddnm_step_scalars* s, void* stream) {
+    if (int e = plus_cs_pre_args(xt, et, et_bstride, aty, x0_out, xt_next, w, B, C, D, ps, s)) return e;
+    if (!noise_ok(noise, s)) return DDNM_E_BADARG;
+    const int64_t chw = (int64_t)C * D * D, total4 = (int64_t)B * chw / 4;
+    DDNM_LAUNCH(cs_plus_pre_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
+                noise_src(noise, s, chw), aty, x0_out, xt_next, w, C, D, ps, chw / 4, total4, *s,
+                CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2});
+    return 0;
+}
+
+extern "C" int ddnm_step_plus_cs_pre_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                               const float* aty, float* x0_out, float* xt_next, float* w, int32_t B,
+                                               int32_t C, int32_t D, int32_t ps, float a_lambda, float d1n, float d2n,
+                                               float dd1, float dd2, const ddnm_step_scalars* s, void* stream) {
+    if (int e = plus_cs_pre_args(xt, et, et_bstride, aty, x0_out, xt_next, w, B, C, D, ps, s)) return e;
+    if (!keys_ok(keys)) return DDNM_E_BADARG;
+    const int64_t chw = (int64_t)C * D * D, total4 = (int64_t)B * chw / 4;
+    DDNM_LAUNCH(cs_plus_pre_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et,
+                et_bstride, keyed_src(keys, s, chw), aty, x0_out, xt_next, w, C, D, ps, chw / 4, total4, *s,
+                CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2});
+    return 0;
+}
+
+// xt_next[img] += P[patch index]: the inverse gather of patchify_kernel with an add (2 reads, 1 write per element)
+__global__ __launch_bounds__(256) void cs_plus_post_kernel(const float* __restrict__ P, float* __restrict__ xn, int D,
+                                                           int ps, int64_t total4) {
+    const int ps4 = ps >> 2, npd = D / ps;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        int64_t t = i;                               // patch-matrix side, as in patchify_kernel
+        const int q = (int)(t % ps4); t /= ps4;
+        const int r = (int)(t % ps); t /= ps;
+        const int px = (int)(t % npd); t /= npd;
+        const int py = (int)(t % npd);
+        const int64_t plane = t / npd;
+        const int64_t img = ((plane * D + py * ps + r) * D + px * ps) + q * 4;
+        st4(xn + img, ld4(xn + img) + ld4(P + i * 4));
+    }
+}
+
+extern "C" int ddnm_step_plus_cs_post_f32(const float* P, float* xt_next, int32_t planes, int32_t D, int32_t ps,
+                                          void* stream) {
+    if (!P || !xt_next || P == xt_next || planes <= 0 || D <= 0 || ps <= 0) return DDNM_E_BADARG;
+    if (D % ps || ps % 4) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)planes * D * D / 4;
+    DDNM_LAUNCH(cs_plus_post_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, P, xt_next, D, ps, total4);
+    return 0;
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // hq_demo sampler (DDPM posterior + DDNM core + mask-shift tiles), hq_demo/guided_diffusion/gaussian_diffusion.py.

@@ -27,7 +27,9 @@ per-class definitions, including its quirk of feeding the RAW patch / needle / p
 the noise and of eps to `V` in `Lambda_noise`.  `SRConv` and `Deblurring2D` define none, like the reference
 (`Lambda` raises NotImplementedError); their DDNM+ runs through the engine hook `ddnm_plus_step` instead
 (`_SpectralPlus`: the whole step fused in the operator's spectral planes, thresholded singular values, eps
-entering as V^T eps).  `Deblurring` opts out of the hook and keeps its `Lambda` / `Lambda_noise`.
+entering as V^T eps).  `Deblurring` opts out of the hook and keeps its `Lambda` / `Lambda_noise`.  `CS` (cs_blockbased)
+has the hook too and no `Lambda` either: all its singular values are 1, so its step collapses per 32x32 patch to one
+image-order pass, the two GEMMs of `A` / `A_pinv` and one scatter-add (`CS.ddnm_plus_step`, `cs_plus_coefficients`).
 """
 import ctypes
 import os
@@ -63,6 +65,15 @@ def spectral_coefficients(s, a, sigma_y, sigma_t, eta):
     if sigma_t > thr:
         return 1.0, (sigma_t ** 2 - a ** 2 * sigma_y ** 2 / s ** 2) ** 0.5, 0.0
     return 1.0, c1, c2
+
+
+def cs_plus_coefficients(a, sigma_y, sigma_t, eta):
+    """The five scalars of the fused DDNM+ step of `CS` (every singular value is 1, svd_operators.py:110):
+    (a*lambda, d1n, d2n, d1r - d1n, d2r - d2n) with (lambda, d1r, d2r) = spectral_coefficients(1, ...) on the measured
+    subspace and (1, d1n, d2n) = spectral_coefficients(0, ...) on the null space; evaluated in double on the host."""
+    lam, d1r, d2r = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)
+    _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
+    return float(a) * lam, d1n, d2n, d1r - d1n, d2r - d2n
 
 
 def _flat(vec):
@@ -788,6 +799,41 @@ class CS(A_functions):
 
     def singulars(self):
         return torch.ones(self.cs_size, device=self.device).repeat(self.channels * self.y_dim ** 2)
+
+    # ---- DDNM+ (sigma_y > 0): the engine hook of `ddnm_plus_diffusion`, like _SpectralPlus.  `Lambda` / `Lambda_noise`
+    # keep raising as in the reference.  All singular values are 1, so with M = Vt_small[:cs] (M^T M projects a patch onto
+    # its measured subspace) the step of functions/svd_ddnm.py:118-131 collapses per patch without the full V_small
+    # (csrc/ddnm_step.hip, ddnm_step_plus_cs_pre_f32 / _post_f32; coefficients: cs_plus_coefficients):
+    #   w       = -a lambda x0 + (d1r - d1n) n + (d2r - d2n) eps
+    #   x_{t-1} = a x0 + d1n n + d2n eps + a lambda A^+ y + unpatch((w M^T) M)
+    # eps enters as V^T eps (here: eps, projected) and n ~ N(0, I) is drawn in the image domain (V is orthogonal).
+    def begin_plus_run(self, y):
+        """Per-run constants: A^+ y as [B, C, D, D] and the scratch of the two GEMMs (w [patches, 1024], T [patches, cs])."""
+        y = _flat(y)
+        B, cs = y.shape[0], self.cs_size
+        if y.shape[1] != self.channels * self.y_dim ** 2 * cs:
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, expected {self.channels} x {self.y_dim ** 2} "
+                             f"patches x {cs}")
+        npatch = self._npatch(B)
+        self._plus_run = (B, self.A_pinv(y).reshape(B, self.channels, self.img_dim, self.img_dim),
+                          torch.empty(npatch, self.ratio ** 2, dtype=torch.float32, device=y.device),
+                          torch.empty(npatch, cs, dtype=torch.float32, device=y.device))
+
+    def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
+        """One DDNM+ reverse step: x0|t into `x0_out` (uncorrected, as the loop returns and time-travels from it), x_{t-1}
+        into `xt_next`.  `et` may be the [:, :3] view of a 6-channel network output (read through its strides).  Four
+        launches: pre kernel, T = w M^T, P = T M (into w's buffer), post kernel."""
+        run = getattr(self, "_plus_run", None)
+        B = xt.shape[0]
+        if run is None or run[0] != B:
+            raise RuntimeError("ddnm_plus_step needs begin_plus_run(y) for this batch first")
+        _, aty, w, T = run
+        ps, ps2, cs, npatch = self.ratio, self.ratio ** 2, self.cs_size, self._npatch(B)
+        coef = cs_plus_coefficients(s.sqrt_at_next, sigma_y, sigma_t, eta)
+        ops.step_plus_cs_pre(xt, et, noise, aty, s, coef, x0_out, xt_next, w, ps)
+        ops.bgemm(w, self.M, T, npatch, cs, ps2, lda=ps2, ldb=ps2, ldc=cs, transb=True)
+        ops.bgemm(T, self.M, w, npatch, ps2, cs, lda=cs, ldb=ps2, ldc=ps2, transb=False)
+        ops.step_plus_cs_post(w, xt_next, ps)
 
 
 class PixelMask(A_functions):

@@ -921,6 +921,42 @@ def step_plus_spectral(xt_hat, et_hat, y_hat, gains, gains_cstride, noise, s, si
     return out
 
 
+def step_plus_cs_pre(xt, et, noise, aty, s, coef, x0_out, xt_next, w, ps):
+    """First kernel of the fused DDNM+ step of block-based CS (include/ddnm_hip.h::ddnm_step_plus_cs_pre_f32): `xt`,
+    `aty` (= A^+ y), `x0_out`, `xt_next` are [B, C, D, D], `et` the same or the [:, :3] view of a 6-channel output, `w` the
+    patch matrix [B*C*(D/ps)^2, ps*ps]; `coef` = svd_operators.cs_plus_coefficients(...); `noise` a tensor, None
+    (in-kernel draw per ddnm_step_scalars::rng_*) or a KeyedPhiloxNoise."""
+    if xt.dim() != 4 or xt.shape[2] != xt.shape[3] or tuple(et.shape) != tuple(xt.shape):
+        raise ValueError(f"step_plus_cs_pre: xt / et must be [B, C, D, D], got {tuple(xt.shape)} / {tuple(et.shape)}")
+    B, C, D = xt.shape[0], xt.shape[1], xt.shape[3]
+    n = B * C * D * D
+    for name, t in (("xt", xt), ("aty", aty), ("x0_out", x0_out), ("xt_next", xt_next), ("w", w)):
+        if _f32c(t, name).numel() != n:
+            raise ValueError(f"step_plus_cs_pre: {name} has {t.numel()} entries, expected {n}")
+    if noise is not None and not isinstance(noise, KeyedPhiloxNoise) and _f32c(noise, "noise").numel() != n:
+        raise ValueError("step_plus_cs_pre: the noise tensor must have one entry per pixel")
+    if et.dtype != torch.float32 or et.stride(0) < C * D * D:
+        raise ValueError("step_plus_cs_pre: et must be fp32 with a batch stride of at least C*D*D")
+    al, d1n, d2n, dd1, dd2 = (float(v) for v in coef)
+    ep, es = _et_args(et)
+    fn, nz = step_noise_args("ddnm_step_plus_cs_pre_f32", noise, xt)
+    check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(aty), _p(x0_out), _p(xt_next), _p(w), B, C, D, int(ps), al, d1n,
+                                  d2n, dd1, dd2, ctypes.byref(s), _stream()), fn)
+
+
+def step_plus_cs_post(P, xt_next, ps):
+    """Last kernel of that step (ddnm_step_plus_cs_post_f32): xt_next [B, C, D, D] += the patch matrix `P`
+    [B*C*(D/ps)^2, ps*ps] scattered back to image order."""
+    if xt_next.dim() != 4 or xt_next.shape[2] != xt_next.shape[3]:
+        raise ValueError(f"step_plus_cs_post: xt_next must be [B, C, D, D], got {tuple(xt_next.shape)}")
+    B, C, D = xt_next.shape[0], xt_next.shape[1], xt_next.shape[3]
+    if _f32c(P, "P").numel() != _f32c(xt_next, "xt_next").numel():
+        raise ValueError(f"step_plus_cs_post: P has {P.numel()} entries, expected {xt_next.numel()}")
+    check(_lib.lib().ddnm_step_plus_cs_post_f32(_p(P), _p(xt_next), B * C, D, int(ps), _stream()),
+          "ddnm_step_plus_cs_post_f32")
+    return xt_next
+
+
 def fill_(t, value=0.0):
     """t[...] = value for a contiguous fp32 tensor (or contiguous slice) through ddnm_fill_f32."""
     if t.numel():

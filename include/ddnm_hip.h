@@ -615,6 +615,31 @@ int ddnm_wh_scatter_f32(const float* y, const int32_t* perm, float* planes, int3
  * Vt_small / V_small (:108-109) then act as one ddnm_bgemm_f32 over all patches.  D % ps == 0, ps % 4 == 0. */
 int ddnm_patchify_f32(const float* src, float* dst, int32_t planes, int32_t D, int32_t ps, int32_t inverse, void* stream);
 
+/* One fused DDNM+ step (functions/svd_ddnm.py:118-131) of block-based CS (svd_operators.py:101-159), per ps x ps patch.
+ * All singular values are 1, so with M = Vt_small[:cs] (orthonormal rows), a = s->sqrt_at_next, sigma_t = sqrt(1 - abar_t'),
+ * (lambda, d1r, d2r) the spectral coefficients of singular value 1, (1, d1n, d2n) those of the null space, n ~ N(0, I):
+ *   x0      = (xt - et * sqrt_1m_at) / sqrt_at
+ *   w       = -a lambda x0 + (d1r - d1n) n + (d2r - d2n) et                 patch layout [B*C*(D/ps)^2][ps*ps]
+ *   x_{t-1} = a x0 + d1n n + d2n et + a lambda A^+y + unpatch((w M^T) M)
+ * which is a (x0 - Lambda A^+ (A x0 - y)) + V (d1 .* V^T n + d2 .* V^T et).  `pre` makes one pass over [B][C][D][D]: it
+ * writes x0 into x0_out, the image-order terms of x_{t-1} into xt_next and w at the positions of ddnm_patchify_f32; the
+ * caller then forms P = (w M^T) M with two ddnm_bgemm_f32 launches and `post` adds it: xt_next[img] += P[patch].
+ * a_lambda = a*lambda, dd1 = d1r - d1n, dd2 = d2r - d2n are evaluated on the host.  et row b at et + b*et_bstride (the
+ * [:, :3] view of a 6-channel output); aty = A^+ y, [B][C][D][D].  noise: a tensor [B][C*D*D], or NULL with s->rng_on
+ * (drawn in-kernel at the image-order index, counter (r / 4, rng_iter, rng_image_base + b, 0), r = index inside the
+ * image: the values of ddnm_randn_philox_f32 on [B][C*D*D]); the keyed form takes the per-image key table instead.
+ * NULL pointer / non-positive size: DDNM_E_BADARG; D % ps, ps % 4 or et_bstride % 4 != 0: DDNM_E_SHAPE; no output may
+ * alias an input or another output (xt_next == xt, et or x0_out; P == xt_next): DDNM_E_BADARG. */
+int ddnm_step_plus_cs_pre_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* aty,
+                              float* x0_out, float* xt_next, float* w, int32_t B, int32_t C, int32_t D, int32_t ps,
+                              float a_lambda, float d1n, float d2n, float dd1, float dd2, const ddnm_step_scalars* s,
+                              void* stream);
+int ddnm_step_plus_cs_pre_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                    const float* aty, float* x0_out, float* xt_next, float* w, int32_t B, int32_t C,
+                                    int32_t D, int32_t ps, float a_lambda, float d1n, float d2n, float dd1, float dd2,
+                                    const ddnm_step_scalars* s, void* stream);
+int ddnm_step_plus_cs_post_f32(const float* P, float* xt_next, int32_t planes, int32_t D, int32_t ps, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * hq_demo sampler: DDPM posterior step with the DDNM core and the mask-shift tiles
  * (hq_demo/guided_diffusion/gaussian_diffusion.py:246-404,430-487,664-746).
