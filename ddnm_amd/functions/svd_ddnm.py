@@ -17,7 +17,24 @@ Reference quirks kept on purpose: float timesteps
 hard-coded class 951 (:7,49-52); time travel re-noises the UN-projected x0
 prediction (:72-74).
 
-`noise` (optional) is an explicit tape: tensor [n_iters, B, 3, H, W] or a list of
+ONE driver, `_reverse_loop`, runs the loop of all three samplers
+(`ddnm_diffusion`, `ddnm_plus_diffusion`, and `simplified_loop` of
+guided_diffusion/diffusion.py): the jump schedule and alpha-bar table, the
+coercion of `x` / `y`, `x0_t` and the two ping-pong buffers, the per-run tables,
+classifier guidance on its side stream, the model call, the time-travel
+re-noise and the `record` probe.  A sampler supplies its per-run operator set-up
+(`begin`) and ONE `step(it, xt, et, y, noise, x0_t, out)` callable: the reverse
+step from eps to `x0_t` and `out`.
+
+Noise reaches the loop as an object with two methods.  `kernel_arg(s, k)` is
+what a step kernel takes as `noise` for loop iteration k: a tensor (`_TapeNoise`,
+`_AtenNoise`), or -- after stamping (on, k) into the step scalars `s` -- None
+(`ops.PhiloxNoise`) or the object itself (`ops.KeyedPhiloxNoise`, which owns the
+key table); then the kernel draws N(0, I) itself.  `tensor(k, like)` is the same
+draw as a tensor (time-travel re-noise, the generic DDNM+ chain).  An iteration
+calls one of the two, once.
+
+The samplers' `noise` argument (optional) is an explicit tape: tensor [n_iters, B, 3, H, W] or a list of
 tensors, consumed one per loop iteration (the parity path).  Without it the
 N(0, I) draw of the reference's `torch.randn_like(x)` (svd_ddnm.py:65,74) happens
 INSIDE the step kernels (`ops.PhiloxNoise`: Philox4x32-10 + Box-Muller, counter =
@@ -35,12 +52,14 @@ drawing exactly what it draws when restored alone.
 benchmark and the parity tests pass False and keep the result in HBM.  `record(k, name, tensor)`
 is an optional probe called with the device tensors `x0_t` / `xt_next` after iteration k.
 """
+import collections
 import contextlib
+import os
 
 import torch
 
-from .. import ops
-from .svd_operators import A_functions
+from .. import _lib, ops
+from .svd_operators import A_functions, _axpby
 
 class_num = 951      # svd_ddnm.py:7
 
@@ -88,8 +107,6 @@ class _AlphaTable:
 def _guided_eps(et, grad, coef):
     """eps[:, :3] - sqrt(1 - abar_t) * cls_fn(x, t, y)   (svd_ddnm.py:51-52; note the guidance is evaluated on the
     INITIAL noise x, not on x_t -- reference quirk kept)."""
-    import ctypes  # noqa: F401
-    from .. import _lib
     n = et.shape[0]
     chw = 3 * et.shape[2] * et.shape[3]
     out = torch.empty(n, 3, et.shape[2], et.shape[3], dtype=torch.float32, device=et.device)
@@ -99,11 +116,16 @@ def _guided_eps(et, grad, coef):
     return out
 
 
+def _reverse_times(times, skip):
+    """The float-timestep values (990, 980, ...) of the schedule's reverse steps, in loop order."""
+    return [a * skip for a, c in zip(times[:-1], times[1:]) if c < a]
+
+
 def _step_tables(times, skip, n, device, with_classes):
     """Per-run device constants of the loop: one row [n] of the float timestep per distinct reverse-step time (the
     reference builds `torch.ones(n) * i` every step, svd_ddnm.py:40) and the constant class vector (:50).  ONE host-to-
     device copy per run; the loop then only takes views -- no fill kernel (and no other ATen arithmetic) per step."""
-    uniq = sorted({a * skip for a, c in zip(times[:-1], times[1:]) if c < a})
+    uniq = sorted(set(_reverse_times(times, skip)))
     table = torch.tensor([[float(v)] * n for v in uniq], dtype=torch.float32).to(device, non_blocking=False) if uniq else None
     index = {v: k for k, v in enumerate(uniq)}
     cls = torch.tensor([class_num] * n, dtype=torch.long).to(device) if with_classes else None
@@ -137,8 +159,6 @@ class _GuidanceAhead:
     restores the serial order on the main stream."""
 
     def __init__(self, cls_fn, x, n, t_values, t_of=None, cls=None):
-        import collections
-        import os
         self.cls_fn, self.x, self.n = cls_fn, x, n
         self.t_of, self.cls = t_of, cls
         self.t_values, self.pos = t_values, 0
@@ -245,70 +265,76 @@ def _philox_for_call(like):
     return ops.PhiloxNoise(z ^ (z >> 31))
 
 
-def _noise_source(noise, like):
-    """draw(k) -> the noise tensor of loop iteration k, or None when the step kernels draw it themselves (`.philox`)."""
-    import os
-    if noise is None and os.environ.get("DDNM_NOISE") == "torch":
-        def draw(k):
-            return torch.randn_like(like)
-        draw.philox = None
-        return draw
-    if isinstance(noise, ops.KeyedPhiloxNoise):
-        # per-image keys: the step kernels get the key table (their keyed entry points), x_T / re-noise / DDNM+ eps use
-        # `.philox.tensor`
-        def keyed(k):
-            return noise
-        keyed.philox = noise
-        return keyed
-    if noise is None or isinstance(noise, ops.PhiloxNoise):
-        ph = _philox_for_call(like) if noise is None else noise
+class _TensorNoise:
+    """A noise source whose draws are tensors; `like` is the template of the kernel-form draw (x: fp32, contiguous)."""
 
-        def draw(k):
-            return None
-        draw.philox = ph
-        return draw
+    def __init__(self, like):
+        self.like = like.float().contiguous()
 
-    def take(k):
-        n = noise[k]
+    def kernel_arg(self, s, k):
+        return self.tensor(k, self.like)
+
+
+class _TapeNoise(_TensorNoise):
+    """An explicit tape, read `tape[k]` once per loop iteration (BatchNoise / FusedTape draw sequentially)."""
+
+    def __init__(self, tape, like):
+        super().__init__(like)
+        self.tape = tape
+
+    def tensor(self, k, like):
+        n = self.tape[k]
         if n.device != like.device or n.dtype != torch.float32 or not n.is_contiguous():
             n = n.to(device=like.device, dtype=torch.float32).contiguous()
         return n
-    take.philox = None
-    return take
 
 
-def _finish(xt, x0_t, return_cpu):
-    if return_cpu:
-        return [xt.to("cpu")], [x0_t.to("cpu")]
-    return [xt], [x0_t]
+class _AtenNoise(_TensorNoise):
+    """The reference's draw: one `torch.randn_like` per loop iteration from the device generator."""
+
+    def tensor(self, k, like):
+        return torch.randn_like(like)
 
 
-def ddnm_diffusion(x, model, b, eta, A_funcs, y, cls_fn=None, classes=None, config=None, noise=None, return_cpu=True,
-                   record=None):
-    if not x.is_cuda:
-        raise RuntimeError("ddnm_amd.ddnm_diffusion runs on the GPU only (no CPU fallback); got a CPU tensor")
-    skip = config.diffusion.num_diffusion_timesteps // config.time_travel.T_sampling
-    n = x.size(0)
-    times = get_schedule_jump(config.time_travel.T_sampling, config.time_travel.travel_length,
-                              config.time_travel.travel_repeat)
+def _noise_source(noise, like):
+    """The noise source (`kernel_arg(s, k)` / `tensor(k, like)`, see the module docstring) of a sampler's `noise`
+    argument: a Philox object as it is, a per-call Philox key for None (the ATen draw with DDNM_NOISE=torch), else a tape."""
+    if isinstance(noise, (ops.PhiloxNoise, ops.KeyedPhiloxNoise)):
+        return noise
+    if noise is not None:
+        return _TapeNoise(noise, like)
+    return _AtenNoise(like) if os.environ.get("DDNM_NOISE") == "torch" else _philox_for_call(like)
+
+
+_Iter = collections.namedtuple("_Iter", "k i at at_next")       # loop index, float timestep, alpha-bar of t and of t'
+
+
+def _reverse_loop(x, model, b, y, config, noise, step, begin=None, cls_fn=None, record=None):
+    """The reverse loop of every sampler here -> (x_0, last un-projected x0 prediction), both on x's device.
+
+    `noise` is a noise source; `begin(y)`, when given, is the operator's per-run set-up and gets the SAME `y` tensor that
+    every step gets (WalshHadamardCS keys its A^+ y on that object).  `step(it, xt, et, y, noise, x0_t, out)` is one
+    reverse step: `it` = _Iter(k, i, at, at_next), `et` the model's eps -- guided when `cls_fn` is given, the [:, :3]
+    view of a learn_sigma output -- and it writes the x0 prediction to `x0_t` and x_t' to `out`, drawing its noise as
+    `noise.kernel_arg(s, it.k)` or `noise.tensor(it.k, x0_t)`.  The caller's `x` is never written."""
+    tt = config.time_travel
+    skip = config.diffusion.num_diffusion_timesteps // tt.T_sampling
+    times = get_schedule_jump(tt.T_sampling, tt.travel_length, tt.travel_repeat)
     alpha = _AlphaTable(b)
+    n = x.size(0)
     x = x.float().contiguous()
     y = y.reshape(n, -1).float().contiguous()
-    draw = _noise_source(noise, x)
-    fused = isinstance(A_funcs, A_functions)
-    if hasattr(A_funcs, "begin_run"):
-        A_funcs.begin_run(y)           # per-run constants of the operator (e.g. A^+ y); never cached across runs
-
+    if begin is not None:
+        begin(y)           # per-run constants of the operator (e.g. A^+ y); never cached across runs
     xt = x
     x0_t = torch.empty_like(x)
     bufs = [torch.empty_like(x), torch.empty_like(x)]
     have_x0 = False
-    guide = None
-    with torch.no_grad(), contextlib.ExitStack() as _stack:
-        t_of, cls_const = _step_tables(times, skip, n, x.device, cls_fn is not None)
+    with torch.no_grad(), contextlib.ExitStack() as stack:
+        t_of, cls = _step_tables(times, skip, n, x.device, cls_fn is not None)
         if cls_fn is not None:
-            guide = _GuidanceAhead(cls_fn, x, n, [a * skip for a, c in zip(times[:-1], times[1:]) if c < a], t_of, cls_const)
-            _stack.callback(guide.close)         # also when the loop raises: the main stream re-joins the side stream
+            guide = _GuidanceAhead(cls_fn, x, n, _reverse_times(times, skip), t_of, cls)
+            stack.callback(guide.close)          # also when the loop raises: the main stream re-joins the side stream
         for k, (i, j) in enumerate(zip(times[:-1], times[1:])):
             i, j = i * skip, j * skip
             if j < 0:
@@ -321,29 +347,44 @@ def ddnm_diffusion(x, model, b, eta, A_funcs, y, cls_fn=None, classes=None, conf
                 if cls_fn is None:
                     et = model(xt, t)
                 else:
-                    cls = cls_const
-                    eps = model(xt, t, cls)
-                    et = _guided_eps(eps, guide.grad(i, t, cls), float((1 - at).sqrt()))
+                    et = _guided_eps(model(xt, t, cls), guide.grad(i, t, cls), float((1 - at).sqrt()))
                 if et.size(1) == 6:
-                    et = et[:, :3]
-                s = ops.step_scalars(at, at_next, eta)
-                if draw.philox is not None:
-                    draw.philox.stamp(s, k)          # the step kernel draws its own noise (noise pointer NULL)
-                if fused:
-                    A_funcs.ddnm_step(xt, et, draw(k), y, s, x0_t, out)
-                else:          # foreign operator object: its own A / A_pinv, our elementwise kernels
-                    ops.step_x0(xt, et, s, out=x0_t)
-                    proj = A_funcs.A_pinv(A_funcs.A(x0_t.reshape(n, -1)) - y).reshape(*x0_t.size())
-                    ops.step_combine(x0_t, proj.float().contiguous(), None, draw(k), et, s, out=out)
+                    et = et[:, :3]               # read through its strides, no copy
+                step(_Iter(k, i, at, at_next), xt, et, y, noise, x0_t, out)
                 have_x0 = True
             else:          # time-travel back (svd_ddnm.py:70-76)
                 assert have_x0
-                nz = draw(k) if draw.philox is None else draw.philox.tensor(k, x0_t)
-                ops.renoise(x0_t, nz, float(at_next.sqrt()), float((1 - at_next).sqrt()), out=out)
+                ops.renoise(x0_t, noise.tensor(k, x0_t), float(at_next.sqrt()), float((1 - at_next).sqrt()), out=out)
             xt = out
             if record is not None:
                 record(k, "x0_t", x0_t)
                 record(k, "xt_next", xt)
+    return xt, x0_t
+
+
+def _finish(xt, x0_t, return_cpu):
+    if return_cpu:
+        return [xt.to("cpu")], [x0_t.to("cpu")]
+    return [xt], [x0_t]
+
+
+def ddnm_diffusion(x, model, b, eta, A_funcs, y, cls_fn=None, classes=None, config=None, noise=None, return_cpu=True,
+                   record=None):
+    if not x.is_cuda:
+        raise RuntimeError("ddnm_amd.ddnm_diffusion runs on the GPU only (no CPU fallback); got a CPU tensor")
+    fused = isinstance(A_funcs, A_functions)
+
+    def step(it, xt, et, y, noise, x0_t, out):
+        s = ops.step_scalars(it.at, it.at_next, eta)
+        if fused:
+            A_funcs.ddnm_step(xt, et, noise.kernel_arg(s, it.k), y, s, x0_t, out)
+        else:          # foreign operator object: its own A / A_pinv, our elementwise kernels
+            ops.step_x0(xt, et, s, out=x0_t)
+            proj = A_funcs.A_pinv(A_funcs.A(x0_t.reshape(x0_t.size(0), -1)) - y).reshape(*x0_t.size())
+            ops.step_combine(x0_t, proj.float().contiguous(), None, noise.kernel_arg(s, it.k), et, s, out=out)
+
+    xt, x0_t = _reverse_loop(x, model, b, y, config, _noise_source(noise, x), step,
+                             begin=getattr(A_funcs, "begin_run", None), cls_fn=cls_fn, record=record)
     return _finish(xt, x0_t, return_cpu)
 
 
@@ -362,68 +403,23 @@ def ddnm_plus_diffusion(x, model, b, eta, A_funcs, y, sigma_y, cls_fn=None, clas
     per step (svd_operators._SpectralPlus)."""
     if not x.is_cuda:
         raise RuntimeError("ddnm_amd.ddnm_plus_diffusion runs on the GPU only (no CPU fallback)")
-    skip = config.diffusion.num_diffusion_timesteps // config.time_travel.T_sampling
-    n = x.size(0)
-    times = get_schedule_jump(config.time_travel.T_sampling, config.time_travel.travel_length,
-                              config.time_travel.travel_repeat)
-    alpha = _AlphaTable(b)
-    x = x.float().contiguous()
-    y = y.reshape(n, -1).float().contiguous()
-    draw = _noise_source(noise, x)
-    from .svd_operators import _axpby
     plus_step = getattr(A_funcs, "ddnm_plus_step", None)     # SRConv / Deblurring2D: the step fused in the spectral planes
-    if plus_step is not None:
-        A_funcs.begin_plus_run(y)         # y^ of THIS call's measurement; never cached across runs
-    xt = x
-    x0_t = torch.empty_like(x)
-    bufs = [torch.empty_like(x), torch.empty_like(x)]
-    have_x0 = False
-    guide = None
-    with torch.no_grad(), contextlib.ExitStack() as _stack:
-        t_of, cls_const = _step_tables(times, skip, n, x.device, cls_fn is not None)
-        if cls_fn is not None:
-            guide = _GuidanceAhead(cls_fn, x, n, [a * skip for a, c in zip(times[:-1], times[1:]) if c < a], t_of, cls_const)
-            _stack.callback(guide.close)         # also when the loop raises: the main stream re-joins the side stream
-        for k, (i, j) in enumerate(zip(times[:-1], times[1:])):
-            i, j = i * skip, j * skip
-            if j < 0:
-                j = -1
-            at_next = alpha(j)
-            out = bufs[k & 1]
-            if j < i:
-                at = alpha(i)
-                t = t_of(i)
-                if cls_fn is None:
-                    et = model(xt, t)
-                else:
-                    cls = cls_const
-                    eps = model(xt, t, cls)
-                    et = _guided_eps(eps, guide.grad(i, t, cls), float((1 - at).sqrt()))
-                a, sigma_t = at_next.sqrt(), (1 - at_next).sqrt()
-                s = ops.step_scalars(at, at_next, eta)
-                if plus_step is not None:
-                    if et.size(1) == 6:
-                        et = et[:, :3]               # read through its strides, no copy
-                    if draw.philox is not None:
-                        draw.philox.stamp(s, k)      # the step kernel draws its own noise (noise pointer NULL / key table)
-                    plus_step(xt, et, draw(k), s, sigma_y, float(sigma_t), eta, x0_t, out)
-                else:
-                    if et.size(1) == 6:
-                        et = et[:, :3].contiguous()
-                    ops.step_x0(xt, et, s, out=x0_t)
-                    resid = _axpby(A_funcs.A(x0_t), y, 1.0, -1.0)
-                    corr = A_funcs.Lambda(A_funcs.A_pinv(resid), a, sigma_y, sigma_t, eta).reshape(x.shape)
-                    eps_k = draw(k) if draw.philox is None else draw.philox.tensor(k, x0_t)
-                    nz = A_funcs.Lambda_noise(eps_k, a, sigma_y, sigma_t, eta, et).reshape(x.shape)
-                    s.c1, s.c2, s.lam = 1.0, 0.0, 1.0        # x_t-1 = sqrt(abar') (x0 - corr) + 1 * nz
-                    ops.step_combine(x0_t, corr, None, nz, et, s, out=out)
-                have_x0 = True
-            else:
-                assert have_x0
-                nz = draw(k) if draw.philox is None else draw.philox.tensor(k, x0_t)
-                ops.renoise(x0_t, nz, float(at_next.sqrt()), float((1 - at_next).sqrt()), out=out)
-            xt = out
-            if record is not None:
-                record(k, "x0_t", x0_t)
-                record(k, "xt_next", xt)
+
+    def step(it, xt, et, y, noise, x0_t, out):
+        a, sigma_t = it.at_next.sqrt(), (1 - it.at_next).sqrt()
+        s = ops.step_scalars(it.at, it.at_next, eta)
+        if plus_step is not None:
+            plus_step(xt, et, noise.kernel_arg(s, it.k), s, sigma_y, float(sigma_t), eta, x0_t, out)
+            return
+        et = et.contiguous()                     # a copy only of the [:, :3] view of a learn_sigma output
+        ops.step_x0(xt, et, s, out=x0_t)
+        resid = _axpby(A_funcs.A(x0_t), y, 1.0, -1.0)
+        corr = A_funcs.Lambda(A_funcs.A_pinv(resid), a, sigma_y, sigma_t, eta).reshape(x0_t.shape)
+        nz = A_funcs.Lambda_noise(noise.tensor(it.k, x0_t), a, sigma_y, sigma_t, eta, et).reshape(x0_t.shape)
+        s.c1, s.c2, s.lam = 1.0, 0.0, 1.0        # x_t-1 = sqrt(abar') (x0 - corr) + 1 * nz
+        ops.step_combine(x0_t, corr, None, nz, et, s, out=out)
+
+    # begin_plus_run: y^ of THIS call's measurement; never cached across runs
+    xt, x0_t = _reverse_loop(x, model, b, y, config, _noise_source(noise, x), step,
+                             begin=A_funcs.begin_plus_run if plus_step is not None else None, cls_fn=cls_fn, record=record)
     return _finish(xt, x0_t, return_cpu)

@@ -30,7 +30,8 @@ import torch.utils.data as data
 
 from .. import dist as ddist
 from .. import ops
-from ..functions.svd_ddnm import _AlphaTable, ddnm_diffusion, ddnm_plus_diffusion, get_schedule_jump
+from ..functions.svd_ddnm import (_AtenNoise, _reverse_loop, _TapeNoise, ddnm_diffusion, ddnm_plus_diffusion,
+                                  get_schedule_jump)
 from ..functions.svd_operators import (Colorization, Denoising, Inpainting, InpaintingBank, PerImageInpainting,
                                       SuperResolution, build_operator, mask_color_sr)
 from .models import Model
@@ -656,40 +657,18 @@ class Diffusion(object):
 def simplified_loop(x, model, betas, eta, op, y, sigma_y, config, noise=None):
     """The loop inlined in the reference at diffusion.py:333-397: Eq. 19 lambda_t / gamma_t with
     sigma_t = sqrt(1 - alpha_bar'^2) (sic, :356) and the whole noise term scaled by gamma_t (:384)."""
-    tt = config.time_travel
-    skip = config.diffusion.num_diffusion_timesteps // tt.T_sampling
-    times = get_schedule_jump(tt.T_sampling, tt.travel_length, tt.travel_repeat)
-    alpha = _AlphaTable(betas)
-    n = x.shape[0]
-    y = y.reshape(n, -1).float().contiguous()
-    xt = x.float().contiguous()
-    x0_t = torch.empty_like(xt)
-    bufs = [torch.empty_like(xt), torch.empty_like(xt)]
-    if hasattr(op, "begin_run"):
-        op.begin_run(y)
-    with torch.no_grad():
-        for k, (i, j) in enumerate(zip(times[:-1], times[1:])):
-            i, j = i * skip, j * skip
-            if j < 0:
-                j = -1
-            at_next = alpha(j)
-            out = bufs[k & 1]
-            nz = torch.randn_like(xt) if noise is None else noise[k]
-            if j < i:
-                at = alpha(i)
-                sigma_t = (1 - at_next ** 2).sqrt()
-                et = model(xt, torch.full((n,), float(i), device=xt.device))
-                if et.size(1) == 6:
-                    et = et[:, :3]
-                if sigma_t >= at_next * sigma_y:
-                    lambda_t = 1.0
-                    gamma_t = float((sigma_t ** 2 - (at_next * sigma_y) ** 2).sqrt())
-                else:
-                    lambda_t = float(sigma_t / (at_next * sigma_y))
-                    gamma_t = 0.0
-                s = ops.step_scalars(at, at_next, eta, lam=lambda_t, gamma=gamma_t)
-                op.ddnm_step(xt, et, nz, y, s, x0_t, out)
-            else:
-                ops.renoise(x0_t, nz, float(at_next.sqrt()), float((1 - at_next).sqrt()), out=out)
-            xt = out
-    return xt
+    def step(it, xt, et, y, noise, x0_t, out):
+        at_next = it.at_next
+        sigma_t = (1 - at_next ** 2).sqrt()
+        if sigma_t >= at_next * sigma_y:
+            lambda_t = 1.0
+            gamma_t = float((sigma_t ** 2 - (at_next * sigma_y) ** 2).sqrt())
+        else:
+            lambda_t = float(sigma_t / (at_next * sigma_y))
+            gamma_t = 0.0
+        s = ops.step_scalars(it.at, at_next, eta, lam=lambda_t, gamma=gamma_t)
+        op.ddnm_step(xt, et, noise.kernel_arg(s, it.k), y, s, x0_t, out)
+
+    # the noise is ATen's here, never the in-kernel draw: the runner replays its draw order into tapes when it fuses
+    source = _AtenNoise(x) if noise is None else _TapeNoise(noise, x)
+    return _reverse_loop(x, model, betas, y, config, source, step, begin=getattr(op, "begin_run", None))[0]

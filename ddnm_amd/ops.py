@@ -783,6 +783,10 @@ class PhiloxNoise:
         s.rng_on, s.rng_seed_lo, s.rng_seed_hi, s.rng_iter, s.rng_image_base = 1, self.seed_lo, self.seed_hi, int(k), self.image_base
         return s
 
+    def kernel_arg(self, s, k):
+        """What a step kernel takes as `noise` for loop iteration k: None, with the draw stamped into `s`."""
+        self.stamp(s, k)
+
     def tensor(self, k, like):
         B = like.shape[0]
         out = torch.empty(like.shape, dtype=torch.float32, device=like.device)
@@ -833,6 +837,11 @@ class KeyedPhiloxNoise:
     def stamp(self, s, k):
         s.rng_on, s.rng_iter = 1, int(k)
         return s
+
+    def kernel_arg(self, s, k):
+        """What a step kernel takes as `noise` for loop iteration k: this object (the key table), `s` stamped."""
+        self.stamp(s, k)
+        return self
 
     def _check_batch(self, B):
         if B != len(self.keys):
