@@ -125,7 +125,8 @@ __global__ __launch_bounds__(256) void bgemm_f32_kernel(const ddnm_gemm_desc d, 
 }
 
 
-// Fallback for shapes the MFMA tiling does not cover (tiny test sizes): one thread per output.
+// Fallback for shapes the MFMA tiling does not cover: one thread per output.  Not only test sizes: cs_blockbased at
+// --deg_scale 0.1 (cs = 102), GeneralA and sr_averagepooling x8 with batch * sites % 64 != 0 run here.
 __global__ __launch_bounds__(256) void bgemm_naive_kernel(const ddnm_gemm_desc d) {
     const int64_t per = (int64_t)d.M * d.N;
     const int64_t total = per * d.batch;

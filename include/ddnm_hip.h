@@ -331,8 +331,11 @@ int ddnm_amax_bound_f32(const float* src0, int64_t per_image0, int32_t kind0, co
  * batch index i -> (i / inner, i % inner); offset = outer*stride_o + inner*stride_i per operand.
  * Replaces torch.bmm / einsum in attention (models.py:171-185; unet.py:344-354) and the
  * separable A / A^+ products of SRConv (functions/svd_operators.py:853-859,893-900).
- * MFMA path: M, N multiples of 64, K multiple of 32, 16-byte aligned rows; any other shape runs a
- * scalar fallback kernel (tiny test sizes only).
+ * MFMA path: M, N multiples of 64, K multiple of 32, lda / ldb and the A / B batch strides multiples of 4, A and B
+ * 16-byte aligned (128x128 tiles when M, N are multiples of 128 and the launch has >= 256 of them, else 64x64);
+ * any other shape runs a scalar fallback kernel, one thread per output.  Production reaches the fallback:
+ * cs_blockbased at --deg_scale 0.1 (cs = 102: N of A, K of A^+), GeneralA, and sr_averagepooling at ratio >= 8
+ * when batch * sites is no multiple of 64.
  * ------------------------------------------------------------------------- */
 typedef struct ddnm_gemm_desc {
     const float* A; const float* Bm; const float* D; float* C;
