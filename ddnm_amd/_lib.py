@@ -243,6 +243,9 @@ PROTOTYPES = {
     "ddnm_wh_gather_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_wh_scatter_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_finalize_psnr_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
+    "ddnm_ssim_workspace_elems": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "ddnm_ssim_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                c_int32, c_void_p]),
 }
 
 _lib = None

@@ -19,7 +19,10 @@ Deliberate differences at the boundary (not in the results):
     leaves most of the chip idle.  Files, PSNR lines and totals are those of the unfused run;
   * `--deg inpainting` with a 3-D `exp/inp_masks/mask.npy` [N, S, S] restores every image with its own hole: the image
     written as `{i}_0.png` uses mask i % N (`restored_images`), in every sharding and fusing mode.  The reference holds
-    one mask per run; a 2-D file behaves as there.
+    one mask per run; a 2-D file behaves as there;
+  * DDNM_METRICS=ssim adds the SSIM column of the paper's tables: an `SSIM: %.4f` line (running mean) after every
+    `PSNR:` line and `Total Average SSIM: %.4f` after the total (ops.ssim, csrc/metrics.hip).  Unset, nothing changes.
+    The averages and, with the switch, this rank's per-image values stay on the runner as `last_metrics`.
 """
 import os
 import random
@@ -255,6 +258,66 @@ def fuse_batches():
     return k
 
 
+# DDNM_METRICS: comma-separated metrics reported NEXT TO the PSNR (unset / empty = PSNR alone, today's output)
+METRICS = ("ssim",)
+SSIM_MIN_SIZE = 11          # the 11x11 window needs one valid position
+
+
+def extra_metrics(image_size=None):
+    """The metrics DDNM_METRICS asks for, as a tuple of names out of METRICS; `image_size` (when given) is checked against
+    what they need, so that a run that cannot report fails before its first image."""
+    names = tuple(t.strip() for t in os.environ.get("DDNM_METRICS", "").split(",") if t.strip())
+    for t in names:
+        if t not in METRICS:
+            raise ValueError(f"DDNM_METRICS: unknown metric {t!r}; accepted values: {', '.join(METRICS)}")
+    if "ssim" in names and image_size is not None and image_size < SSIM_MIN_SIZE:
+        raise ValueError(f"DDNM_METRICS=ssim needs images of at least {SSIM_MIN_SIZE} x {SSIM_MIN_SIZE} pixels, "
+                         f"got image_size {image_size}")
+    return names
+
+
+class MetricLog:
+    """PSNR (always) and SSIM (DDNM_METRICS=ssim) of the images one rank finishes: running sums for the printed means
+    and, with the switch set, per-image values in the order the images were finished.  `index` names the IMAGE (the i
+    of `Apy/orig_{i}.png`); the simplified runner writes that image's restoration as `{i - 1}_0.png`, like the
+    reference."""
+
+    def __init__(self, image_size):
+        self.with_ssim = "ssim" in extra_metrics(image_size)
+        self.psnr_sum, self.ssim_sum, self.n = 0.0, 0.0, 0
+        self.index, self.psnr, self.ssim = [], [], []
+
+    def add(self, x, x_orig, psnr, idx0):
+        """One finished loader batch: x, x_orig on the [-1, 1] scale, `psnr` from ops.finalize_psnr; prints the lines."""
+        b = x_orig.shape[0]
+        self.psnr_sum += float(psnr.sum())
+        self.n += b
+        print("PSNR: %.2f" % (self.psnr_sum / self.n))
+        if self.with_ssim:
+            self.index += range(idx0, idx0 + b)
+            self.psnr += psnr.double().cpu().tolist()
+            s = ops.ssim(x, x_orig)
+            self.ssim_sum += float(s.sum())
+            self.ssim += s.cpu().tolist()
+            print("SSIM: %.4f" % (self.ssim_sum / self.n))
+
+    def total(self, rank, device, reduce):
+        """Totals over the ranks (`reduce`: the sums live on several ranks) printed by rank 0; returns last_metrics."""
+        if reduce:
+            self.psnr_sum, self.n = ddist.reduce_sum(self.psnr_sum, device), int(ddist.reduce_sum(self.n, device))
+            if self.with_ssim:
+                self.ssim_sum = ddist.reduce_sum(self.ssim_sum, device)
+        n = max(self.n, 1)
+        if rank == 0:
+            print("Total Average PSNR: %.2f" % (self.psnr_sum / n))
+            if self.with_ssim:
+                print("Total Average SSIM: %.4f" % (self.ssim_sum / n))
+            print("Number of samples: %d" % self.n)
+        return {"psnr": self.psnr_sum / n, "ssim": self.ssim_sum / n if self.with_ssim else None, "n": self.n,
+                "index": self.index if self.with_ssim else None, "psnr_per_image": self.psnr if self.with_ssim else None,
+                "ssim_per_image": self.ssim if self.with_ssim else None}
+
+
 # the simplified path pre-draws x_T and every loop iteration's ATen noise of a fused group (to replay the unfused draw
 # order): (n_iter + 1) * K * C * S^2 * 4 bytes, kept under this bound by capping K (celeba / ADM at 256^2, T = 100:
 # 79 MB per image, K <= 27)
@@ -446,8 +509,8 @@ class Diffusion(object):
         rank, world = ddist.world_state()      # the INITIALISED group (env-only sharding without a group loses shards)
         print(f"Start from {args.subset_start}")
         idx_so_far = args.subset_start
-        psnr_sum, n_done = 0.0, 0
         C, S = config.data.channels, config.data.image_size
+        log = MetricLog(S)
         os.makedirs(os.path.join(args.image_folder, "Apy"), exist_ok=True)      # (rank 0 made the image folder before the first barrier)
         # Sharding (one process per GPU): a loader batch of at least `world` images is split by image index and gathered once;
         # SMALLER batches -- every shipped config has sampling.batch_size 1 -- are dealt whole, round-robin, each rank writing
@@ -473,14 +536,11 @@ class Diffusion(object):
                                      args.subset_start)) if bank is not None else None
 
         def finish(x_all, x_orig, idx0):
-            nonlocal psnr_sum, n_done
-            b = x_orig.shape[0]
-            img, psnr = ops.finalize_psnr(x_all.contiguous(), x_orig)
-            for j in range(b):
+            x_all = x_all.contiguous()
+            img, psnr = ops.finalize_psnr(x_all, x_orig)
+            for j in range(x_orig.shape[0]):
                 save_image(img[j], os.path.join(args.image_folder, f"{idx0 + j}_{0}.png"))
-            psnr_sum += float(psnr.sum())
-            n_done += b
-            print("PSNR: %.2f" % (psnr_sum / n_done))
+            log.add(x_all, x_orig, psnr, idx0)
 
         def restore(x, y_loc, classes, noise, A_funcs):
             if bank is not None and A_funcs.rows != [i % len(bank) for i in next(calls)]:
@@ -560,13 +620,9 @@ class Diffusion(object):
             if writer:
                 finish(x_all, x_orig, idx_so_far)
             idx_so_far += b
-        if deal:
-            psnr_sum, n_done = ddist.reduce_sum(psnr_sum, self.device), int(ddist.reduce_sum(n_done, self.device))
-        if rank == 0:
-            print("Total Average PSNR: %.2f" % (psnr_sum / max(n_done, 1)))
-            print("Number of samples: %d" % n_done)
+        self.last_metrics = log.total(rank, self.device, reduce=deal)
         ddist.barrier()
-        return psnr_sum / max(n_done, 1)
+        return self.last_metrics["psnr"]
 
     # ------------------------------------------------------------------ simplified path (diffusion.py:211-415)
     def _simplified_operator(self):
@@ -600,7 +656,7 @@ class Diffusion(object):
         rank, world = ddist.world_state()      # the INITIALISED group (env-only sharding without a group loses shards)
         print(f"Start from {args.subset_start}")
         idx_so_far = args.subset_start
-        psnr_sum, n_done = 0.0, 0
+        log = MetricLog(config.data.image_size)
         os.makedirs(os.path.join(args.image_folder, "Apy"), exist_ok=True)
         # DDNM_FUSE_BATCHES=K: up to K of this rank's images in one loop.  The loop's noise is ATen's (torch.randn), so the
         # unfused draw order -- per image: x_T, then one draw per loop iteration -- is replayed into a tape up front
@@ -612,13 +668,10 @@ class Diffusion(object):
         pending = []
 
         def finish(x, x_orig, idx0):
-            nonlocal psnr_sum, n_done
             img, psnr = ops.finalize_psnr(x, x_orig)
             # the reference names the file with the stale loop variable j = -1 (:402); reproduced
             save_image(img[0], os.path.join(args.image_folder, f"{idx0 + (-1)}_{0}.png"))
-            psnr_sum += float(psnr[0])
-            n_done += x_orig.shape[0]
-            print("PSNR: %.2f" % (psnr_sum / n_done))
+            log.add(x, x_orig, psnr, idx0)
 
         for bi, (x_orig, classes) in enumerate(loader):
             if config.sampling.batch_size != 1:
@@ -647,11 +700,8 @@ class Diffusion(object):
                 x = simplified_loop(x, model, self.betas, args.eta, op, y, sigma_y, config)
                 finish(x, x_orig, idx_so_far)
             idx_so_far += y.shape[0]
-        psnr_sum, n_done = ddist.reduce_sum(psnr_sum, self.device), int(ddist.reduce_sum(n_done, self.device))
-        if rank == 0:
-            print("Total Average PSNR: %.2f" % (psnr_sum / max(n_done, 1)))
-            print("Number of samples: %d" % n_done)
-        return psnr_sum / max(n_done, 1)
+        self.last_metrics = log.total(rank, self.device, reduce=True)
+        return self.last_metrics["psnr"]
 
 
 def simplified_loop(x, model, betas, eta, op, y, sigma_y, config, noise=None):

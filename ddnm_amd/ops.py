@@ -991,3 +991,22 @@ def finalize_psnr(x, x_orig=None, want_img=True):
     if sse is not None:
         psnr = 10.0 * torch.log10(1.0 / (sse / chw))
     return img, psnr
+
+
+def ssim(x, x_orig, transform=True):
+    """Per-image SSIM of `x` against `x_orig` ([B, C, H, W], any C, H and W >= 11) as a float64 tensor [B]
+    (csrc/metrics.hip): transform=True takes the sampler's [-1, 1] tensors exactly as `finalize_psnr` does,
+    transform=False takes [0, 1] images."""
+    if x.dim() != 4 or x.shape != x_orig.shape:
+        raise ValueError(f"ssim: expected two [B, C, H, W] tensors of one shape, got {tuple(x.shape)} and "
+                         f"{tuple(x_orig.shape)}")
+    B, C, H, W = x.shape
+    lib = _lib.lib()
+    n = lib.ddnm_ssim_workspace_elems(B, C, H, W)
+    if n < 0:
+        check(int(n), "ddnm_ssim_workspace_elems")
+    work = torch.empty(n, dtype=torch.float64, device=x.device)
+    out = torch.empty(B, dtype=torch.float64, device=x.device)
+    check(lib.ddnm_ssim_f32(_p(_f32c(x, "x")), _p(_f32c(x_orig, "x_orig")), _p(out), _p(work), n, B, C, H, W,
+                            1 if transform else 0, _stream()), "ddnm_ssim_f32")
+    return out

@@ -665,6 +665,19 @@ int ddnm_hq_sample_f32(const float* x0_hat, const float* xt, const float* grad, 
 int ddnm_finalize_psnr_f32(const float* x, const float* x_orig, float* img /* may be NULL */, double* sse /* [B], zeroed by callee */,
                            int32_t B, int64_t chw, void* stream);
 
+/* SSIM (Wang et al. 2004) of x against y, one double per image: 11x11 Gaussian window (sigma 1.5, weights normalised in
+ * fp64), valid positions only, C1 = 0.01^2, C2 = 0.03^2, ssim[b] = mean of the map over the C*(H-10)*(W-10) positions
+ * of image b.  x, y: NCHW fp32; transform != 0 passes both through clamp((v+1)/2, 0, 1) on load (the sampler's [-1, 1]
+ * tensors, as ddnm_finalize_psnr_f32 takes them), transform == 0 takes [0, 1] images.  Moments are accumulated in fp64
+ * and the per-tile partials are added in a fixed order without atomics: an image's value is bit for bit the same alone
+ * and at any position of any batch.  work: ddnm_ssim_workspace_elems(B, C, H, W) doubles
+ * (= B * C * ceil((W-10)/32) * ceil((H-10)/16), one per 32x16 tile of valid positions), not read after the call.
+ * NULL x / y / ssim / work or B, C <= 0: DDNM_E_BADARG; H < 11, W < 11, more than 2^31-1 tiles or work_elems below
+ * the query: DDNM_E_SHAPE (the query returns the same negative codes). */
+int64_t ddnm_ssim_workspace_elems(int32_t B, int32_t C, int32_t H, int32_t W);
+int ddnm_ssim_f32(const float* x, const float* y, double* ssim /* [B] */, double* work, int64_t work_elems, int32_t B,
+                  int32_t C, int32_t H, int32_t W, int32_t transform, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
