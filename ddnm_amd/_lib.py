@@ -114,6 +114,8 @@ PROTOTYPES = {
     "ddnm_conv3x3_s16_f32": (c_int32, [POINTER(ConvDesc), c_void_p]),
     "ddnm_conv3x3_s16_supported": (c_int32, [POINTER(ConvDesc)]),
     "ddnm_conv3x3_s16_persistent": (c_int32, [POINTER(ConvDesc)]),
+    # ConvDesc.flags bit 1 (DDNM_CONV_UPS_SUBPIXEL) + ups = 1: `weight` is the phase packing (ops.pack_upsample_conv_weight_s16)
+    "ddnm_conv3x3_s16_ups_subpixel_supported": (c_int32, [POINTER(ConvDesc)]),
     "ddnm_conv3x3_s16_workspace_floats": (c_int64, [POINTER(ConvDesc)]),
     "ddnm_conv3x3_s16_stats_tiles": (c_int32, [POINTER(ConvDesc)]),
     "ddnm_conv3x3_s16_act_scale": (c_float, []),

@@ -31,6 +31,11 @@ static inline bool conv_sizes_addressable(const ddnm_conv_desc* d) {
 // persistent form of the split-fp16 3x3 kernel (conv_s16_persist.hip), dispatched from conv_igemm_f16.hip::run_f16
 bool conv3x3_s16_persist_eligible(const ConvArgs& p);
 int conv3x3_s16_persist_launch(const ConvArgs& p, hipStream_t s);
+// sub-pixel form of `nearest x2 -> 3x3` on phase-packed weights (conv_s16_subpixel.hip; ddnm_conv_desc::flags & DDNM_CONV_UPS_SUBPIXEL)
+bool conv3x3_s16_ups_subpixel_ok(const ddnm_conv_desc* d);
+int conv3x3_s16_ups_subpixel_run(const ddnm_conv_desc* d, hipStream_t s);
+// workgroups of a persistent launch: the CU count of the current device rounded down to a multiple of 8, queried once per device
+int conv_persist_grid_cus();
 
 // ---- tile geometry helper: local row r of M-tile -> output pixel
 struct TileMap {

@@ -522,14 +522,20 @@ static int run_f16(const ddnm_conv_desc* d, void* stream, bool split) {
 extern "C" int ddnm_conv3x3_f16_f32(const ddnm_conv_desc* d, void* stream) { return run_f16(d, stream, false); }
 
 // ---- split form: fp32 tensors, fp32-grade products as three fp16 MFMAs (see the kernel's header comment)
-extern "C" int ddnm_conv3x3_s16_f32(const ddnm_conv_desc* d, void* stream) { return run_f16(d, stream, true); }
+// (flags & DDNM_CONV_UPS_SUBPIXEL: `weight` is the phase packing of an upsample convolution -- conv_s16_subpixel.hip, or an error)
+extern "C" int ddnm_conv3x3_s16_f32(const ddnm_conv_desc* d, void* stream) {
+    if (d && (d->flags & DDNM_CONV_UPS_SUBPIXEL)) return conv3x3_s16_ups_subpixel_run(d, (hipStream_t)stream);
+    return run_f16(d, stream, true);
+}
+
+extern "C" int ddnm_conv3x3_s16_ups_subpixel_supported(const ddnm_conv_desc* d) { return conv3x3_s16_ups_subpixel_ok(d) ? 1 : 0; }
 
 extern "C" float ddnm_conv3x3_s16_act_scale(void) { return DDNM_S16_ASCALE; }
 
 // 1: this launch would run the persistent form (conv_s16_persist.hip): >= 2 tiles per CU, no split-K (profiling / bench labels)
 extern "C" int ddnm_conv3x3_s16_persistent(const ddnm_conv_desc* d) {
     PlanF16 pl;
-    if (!d || d->src_f16 || (d->flags & DDNM_CONV_ONE_TILE) || !plan_f16(d, &pl, KC16 / 2) || pl.ksplit != 1) return 0;
+    if (!d || (d->flags & DDNM_CONV_UPS_SUBPIXEL) || d->src_f16 || (d->flags & DDNM_CONV_ONE_TILE) || !plan_f16(d, &pl, KC16 / 2) || pl.ksplit != 1) return 0;
     ConvArgs p;
     p.d = *d;
     p.Cin = d->C0 + d->C1;
@@ -547,12 +553,14 @@ extern "C" int ddnm_conv3x3_s16_supported(const ddnm_conv_desc* d) {
 
 extern "C" int64_t ddnm_conv3x3_s16_workspace_floats(const ddnm_conv_desc* d) {
     PlanF16 pl;
+    if (d && (d->flags & DDNM_CONV_UPS_SUBPIXEL)) return conv3x3_s16_ups_subpixel_ok(d) ? 0 : DDNM_E_SHAPE;      // never split-K
     if (!d || !plan_f16(d, &pl, KC16 / 2)) return DDNM_E_SHAPE;
     return pl.ksplit > 1 ? (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
 }
 
 extern "C" int ddnm_conv3x3_s16_stats_tiles(const ddnm_conv_desc* d) {
     PlanF16 pl;
+    if (d && (d->flags & DDNM_CONV_UPS_SUBPIXEL)) return conv3x3_s16_ups_subpixel_ok(d) ? d->Ho * d->Wo / 256 : DDNM_E_SHAPE;
     if (!d || !plan_f16(d, &pl, KC16 / 2)) return DDNM_E_SHAPE;
     return pl.ksplit > 1 ? splitk_stats_tiles(d) : d->Ho * d->Wo / pl.BM;
 }

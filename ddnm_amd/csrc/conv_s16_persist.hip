@@ -20,7 +20,7 @@
 //
 // Replaces: the same nn.Conv2d 3x3 + Normalize / swish prologue + concat + nearest x2 + temb addend + residual of the
 // celeba `Model` (/root/reference/guided_diffusion/models.py:36-134) as ddnm_conv3x3_s16_f32, for launches of >= 2 tiles per
-// CU without a fused shortcut (the 256^2 / 128^2 levels: 62 % of the forward's kernel time).
+// CU, a ResnetBlock's fused 1x1 shortcut included (the 256^2 / 128^2 levels: 62 % of the forward's kernel time).
 #include <type_traits>
 
 #include "conv_common.h"
@@ -257,7 +257,8 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     const __amdgpu_buffer_rsrc_t r_bias = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.bias)), 0, d.bias ? (unsigned)Cout * 4u : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t r_badd = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(reinterpret_cast<const void*>(d.badd)), 0, d.badd ? (unsigned)d.B * d.badd_stride * 4u : 0u, 0x00020000);
+        const_cast<void*>(reinterpret_cast<const void*>(d.badd)), 0,
+        d.badd ? (unsigned)((d.B - 1) * d.badd_stride + Cout) * 4u : 0u, 0x00020000);      // (badd_stride 0: one row shared by all images)
     const __amdgpu_buffer_rsrc_t r_stats = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<void*>(d.stats_out), 0, d.stats_out ? (unsigned)p.m_tiles * Cout * 8u : 0u, 0x00020000);
     const unsigned o_lane = (unsigned)(((wm * MT * Wo + rsel) * Cout + wn * NT * 32 + ncol) * 4);
@@ -539,11 +540,8 @@ bool conv3x3_s16_persist_eligible(const ConvArgs& p) {
 }
 
 int conv3x3_s16_persist_launch(const ConvArgs& p, hipStream_t s) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
+    const int cus = conv_persist_grid_cus();            // (conv_s16_subpixel.hip: cached per device, a multiple of 8)
     const int total = p.m_tiles * p.n_tiles;
-    cus -= cus % 8;                                     // the XCD-contiguous tile order wants a multiple of 8 workgroups
     const dim3 grid(total < cus ? total : cus);
     const bool asc = p.d.amax_in != nullptr, res = p.d.res != nullptr;
     if (p.d.skip0) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, false, true>), grid, dim3(P_NTHREADS), 0, s, p, total); }

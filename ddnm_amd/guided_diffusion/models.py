@@ -38,6 +38,11 @@ from . import _net
 GN_EPS = 1e-6          # models.py:33
 # DDNM_CONV_F32=mfma32: every convolution on the fp32 MFMA instruction (the pre-split engine; A/B switch)
 SPLIT16 = os.environ.get("DDNM_CONV_F32", "split16") != "mfma32"
+# Upsample convolutions in the sub-pixel form (csrc/conv_s16_subpixel.hip: four 2x2 convolutions on the low-resolution grid, 4/9
+# of the MFMA work).  DDNM_UPS_SUBPIXEL=0: the `ups` path of the 3x3 kernels everywhere (A/B switch); =all: every launch that
+# qualifies; default: launches of at least UPS_SUBPIXEL_MIN_TILES tiles, the ones measured faster (tools/experiments/HISTORY.md)
+UPS_SUBPIXEL = os.environ.get("DDNM_UPS_SUBPIXEL", "1")
+UPS_SUBPIXEL_MIN_TILES = 128
 CIN_PAD = 32           # conv_in reads the image through a 32-channel NHWC staging tensor
 
 
@@ -57,6 +62,7 @@ class Model(_net.GraphedNet):
         """`split16`: run the 3x3 / stride-1 layers on the split-fp16 kernel (None: the DDNM_CONV_F32 default above)."""
         self.config = config
         self.split16 = SPLIT16 if split16 is None else bool(split16)
+        self.ups_subpixel = UPS_SUBPIXEL if self.split16 else "0"      # "0" / "1" / "all", see UPS_SUBPIXEL above
         self.fused_attn = self.split16        # AttnBlock in one launch (csrc/attn_d512.hip, split-fp16 products); the strict
         #                                       fp32 engine keeps the three-launch fp32-MFMA route
         self.fused_attn_max_tokens = 64       # measured: 26.0 -> 17.4 us at T = 64, but 42.1 -> 50.7 us at T = 256 (B = 8)
@@ -272,6 +278,9 @@ class Model(_net.GraphedNet):
                     wu = g(f"up.{lvl}.upsample.conv.weight")
                     su = ops.s16_weight_scale(wu)
                     w[f"up.{lvl}.upsample.conv.s16"] = (ops.pack_conv_weight_s16(wu, su), su, None)
+                    lr = self.resolution >> lvl             # the level's own (low) resolution: 8 x 32 tiles, 64-channel blocks
+                    if c % 64 == 0 and lr % 32 == 0:
+                        w[f"up.{lvl}.upsample.conv.s16_subpixel"] = ops.upsample_weight_s16(wu)
                 w[f"up.{lvl}.upsample.conv.bias"] = g(f"up.{lvl}.upsample.conv.bias")
         w["norm_out.weight"], w["norm_out.bias"] = g("norm_out.weight"), g("norm_out.bias")
         w["conv_out.weight"] = ops.pack_conv_weight(g("conv_out.weight"))
@@ -436,11 +445,24 @@ class Model(_net.GraphedNet):
                     h = self._attn(attns[ib], h)
             if has_up:
                 n = f"up.{lvl}.upsample.conv"
+                if self._ups_subpixel(n, h.t.shape, c):
+                    h = ops.conv2d(h, w[n + ".weight"], c, 3, bias=w[n + ".bias"], ups=True, emit_stats=True,
+                                   weight_s16=w[n + ".s16_subpixel"], ups_subpixel=True)
+                    continue
                 h = ops.conv2d(h, w[n + ".weight"], c, 3, bias=w[n + ".bias"], ups=True, emit_stats=True,
                                weight_s16=w.get(n + ".s16"))
         gn = self._gn(h, None, "norm_out")
         return ops.conv2d(h, w["conv_out.weight"], self.out_ch, 3, gn=gn, gn_silu=True, bias=w["conv_out.bias"],
                           out_nchw=True)
+
+    def _ups_subpixel(self, n, shape, c):
+        """Whether upsample convolution `n` over a low-resolution [B, H, W, c] input runs the sub-pixel form."""
+        if self.ups_subpixel == "0" or (n + ".s16_subpixel") not in self.w:
+            return False
+        B, H, W = shape[0], shape[1], shape[2]
+        if self.ups_subpixel != "all" and B * (H * W // 256) * (c // 32) < UPS_SUBPIXEL_MIN_TILES:
+            return False
+        return ops.conv_runs_ups_subpixel(B, H, W, c, c)
 
     def __call__(self, x, t):
         return self.forward(x, t)

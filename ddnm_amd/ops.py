@@ -182,6 +182,48 @@ def pack_conv_weight_s16(w, scale):
     return torch.cat([hi, lo], 3).contiguous()
 
 
+def upsample_phase_weights(w):
+    """OIHW 3x3 weights of `nearest x2 -> conv3x3(pad 1)` -> the four 2x2 kernels Wp[py][px][O][I][a][b] (fp64) that give the
+    same output on the LOW-resolution grid: out[2y + py][2x + px] = sum_ab Wp[py][px][a][b] . X[y + py - 1 + a][x + px - 1 + b].
+    Row phase 0 sends ky = 0 to offset -1 and ky = 1, 2 to 0; phase 1 sends ky = 0, 1 to 0 and ky = 2 to +1; columns alike."""
+    w = w.detach().to(torch.float64)
+    # sel[p][a][k] = 1 when tap k of phase p lands on 2x2 position a
+    sel = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=torch.float64, device=w.device)
+    return torch.einsum("pak,qbl,oikl->pqoiab", sel, sel, w)
+
+
+UPS_SUBPIXEL = 2          # include/ddnm_hip.h::DDNM_CONV_UPS_SUBPIXEL
+
+
+def pack_upsample_conv_weight_s16(w, scale):
+    """Phase packing of an upsample convolution for ddnm_conv3x3_s16_f32 with DDNM_CONV_UPS_SUBPIXEL: scale * Wp (summed in fp64,
+    `scale` = s16_weight_scale of the SUMMED tensor: |Wp| reaches 4 max|W|) split into hi / lo fp16, as an fp16 tensor
+    [4 Cout][4 steps (a, b)][Cin / 32][2][32] with row ((cb * 2 + py) * 2 + px) * 64 + c for output channel cb * 64 + c."""
+    cout, cin = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3) or cin % 32 or cout % 64:
+        raise ValueError("phase packing needs 3x3 weights, Cin % 32 == 0 and Cout % 64 == 0")
+    wp = upsample_phase_weights(w) * float(scale)                # [py][px][O][I][a][b], power-of-two scaling: exact
+    wp = wp.reshape(2, 2, cout // 64, 64, cin, 4).permute(2, 0, 1, 3, 5, 4).reshape(4 * cout, 4, cin)
+    hi = wp.to(torch.float16)
+    lo = (wp - hi.double()).to(torch.float16)
+    hi, lo = hi.view(4 * cout, 4, cin // 32, 1, 32), lo.view(4 * cout, 4, cin // 32, 1, 32)
+    return torch.cat([hi, lo], 3).contiguous()
+
+
+def upsample_weight_s16(w):
+    """(packed, scale, None) of pack_upsample_conv_weight_s16 with the scale of the summed tensor: `weight_s16` of
+    conv2d(..., ups=True, ups_subpixel=True)."""
+    sc = s16_weight_scale(upsample_phase_weights(w))
+    return (pack_upsample_conv_weight_s16(w, sc), sc, None)
+
+
+def conv_runs_ups_subpixel(B, H, W, cin, cout):
+    """True when `nearest x2 -> 3x3` over a [B, H, W, cin] LOW-resolution input can take the sub-pixel form."""
+    d = _shape_desc(B, 2 * H, 2 * W, cin, cout)
+    d.ups, d.flags = 1, UPS_SUBPIXEL
+    return _lib.lib().ddnm_conv3x3_s16_ups_subpixel_supported(ctypes.byref(d)) == 1
+
+
 def conv_runs_s16(B, H, W, cin, cout, ups=False):
     """True when a 3x3 / stride-1 conv of this OUTPUT shape takes the split-fp16 kernel (given split-packed weights)."""
     return _lib.lib().ddnm_conv3x3_s16_supported(ctypes.byref(_shape_desc(B, H, W, cin, cout))) == 1
@@ -255,8 +297,10 @@ def amax_bound(a0, a1=None):
 def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_stride=0, res=None, res_ups=False,
            gn=None, gn_silu=True, stride=1, pad=None, ups=False, out=None, out_nchw=False, out_hw=None, tile=0,
            emit_stats=False, weight_f16=None, skip=None, skip_weight=None, skip_weight_f16=None, weight_s16=None,
-           raw_amax=None, one_tile=False):
+           raw_amax=None, one_tile=False, ups_subpixel=False):
     """NHWC implicit-GEMM convolution; see include/ddnm_hip.h::ddnm_conv_desc.
+    ups_subpixel=True (with ups=True): `weight_s16` is the PHASE packing (upsample_weight_s16) and the launch runs the
+    sub-pixel form of the split-fp16 kernel; a launch that does not qualify is an error.
     one_tile=True: the split-fp16 3x3 launch runs the one-tile-per-workgroup kernel where the persistent form would apply
     (same results bit for bit; A/B timing and the bit-identity tests).
     With emit_stats=True returns an `Act` (tensor + GroupNorm partials when the launch can produce them).
@@ -290,6 +334,12 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     d.badd_stride, d.tile, d.res_ups = badd_stride, tile, int(res_ups)
     d.flags = 1 if (one_tile or FORCE_ONE_TILE) else 0
     L = _lib.lib()
+    if ups_subpixel:
+        d.flags = UPS_SUBPIXEL
+        if (not ups or weight_s16 is None or weight_f16 is not None or skip is not None
+                or L.ddnm_conv3x3_s16_ups_subpixel_supported(ctypes.byref(d)) != 1):
+            raise ValueError(f"ups_subpixel: launch (B={B}, {Hs}x{Ws} -> {Ho}x{Wo}, Cin={C0 + C1}, Cout={cout}) does not "
+                             "qualify (ddnm_conv3x3_s16_ups_subpixel_supported)")
     if out_nchw and cout <= 4 and skip is None and weight_f16 is None and L.ddnm_conv3x3_small_cout_f32_supported(ctypes.byref(d)) == 1:
         # the network's 3-channel output convolution: HBM-bound vector-ALU kernel (csrc/conv_small_f32.hip)
         _launch(L.ddnm_conv3x3_small_cout_f32, d, "ddnm_conv3x3_small_cout_f32",
@@ -306,7 +356,7 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
         s0, s1 = tensor_of(skip[0]), tensor_of(skip[1])
         d.skip0, d.skip1 = _p(s0), _p(s1)
         d.SC0, d.SC1 = s0.shape[3], (0 if s1 is None else s1.shape[3])
-    s16 = (weight_s16 is not None and weight_f16 is None and ksize == 3 and stride == 1
+    s16 = ups_subpixel or (weight_s16 is not None and weight_f16 is None and ksize == 3 and stride == 1
            and (skip is None or (weight_s16[2] is not None and gn is not None and d.SC0 % 32 == 0 and d.SC1 % 32 == 0))
            and L.ddnm_conv3x3_s16_supported(ctypes.byref(d)) == 1)
     # ... and the per-tap gather form of the same arithmetic for 1x1 / strided / 8x8-level launches (no fused shortcut)
@@ -388,7 +438,8 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
         elif f16:
             variant = "conv3x3_halo_f16<256x128>"
         elif s16:
-            variant = "conv3x3_s16_persist<256x128>" if L.ddnm_conv3x3_s16_persistent(ctypes.byref(d)) == 1 else "conv3x3_halo_s16<256x128>"
+            variant = ("conv2x2x4_s16_subpixel<256x128>" if ups_subpixel else
+                       "conv3x3_s16_persist<256x128>" if L.ddnm_conv3x3_s16_persistent(ctypes.byref(d)) == 1 else "conv3x3_halo_s16<256x128>")
         elif s16g:
             variant = "conv_gather_s16"
         else:
@@ -396,6 +447,8 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
             kind = "conv3x3_halo_f32" if (ksize == 3 and stride == 1) else "conv_gather_f32"
             variant = kind + {128: "<128x128>", 64: "<64x64>", 32: "<128x32>"}[tn]
         flops = 2.0 * B * Ho * Wo * cout * (ksize * ksize * (C0 + C1) + d.SC0 + d.SC1)      # + fused 1x1 shortcut
+        if ups_subpixel:
+            flops *= 16.0 / 36.0                       # 4 of 9 taps per output pixel: the FLOPs the launch issues
         return variant, flops, (B, Ho, Wo, C0 + C1, cout, ksize, stride, int(ups), d.SC0 + d.SC1, gn is not None,
                                 res is not None)
     _launch(fn_run, d, "ddnm_conv2d", record)

@@ -91,7 +91,9 @@ typedef struct ddnm_conv_desc {
     float acc_scale;        /* ddnm_conv3x3_s16_f32 only: power of two that multiplies the accumulator before bias / residual
                                (undoes the operand pre-scaling of the split form); ignored by the other entry points */
     int32_t flags;          /* bit 0 (DDNM_CONV_ONE_TILE): ddnm_conv3x3_s16_f32 runs the one-tile-per-workgroup kernel even where
-                               the persistent form (>= 2 tiles per CU) applies -- same results bit for bit; for A/B timing */
+                               the persistent form (>= 2 tiles per CU) applies -- same results bit for bit; for A/B timing
+                               bit 1 (DDNM_CONV_UPS_SUBPIXEL): ddnm_conv3x3_s16_f32 with ups = 1 takes `weight` as the PHASE
+                               packing of the upsample convolution (see ddnm_conv3x3_s16_ups_subpixel_supported) */
     /* ABI 5 -- operand-range guard of the split forms (ddnm_conv3x3_s16_f32, ddnm_conv_gather_s16_f32; ignored by every
      * other entry point).  fp16 carries |v| < 65504 only, fp32 -- the arithmetic the reference runs -- does not care, so
      * operands the kernel reads RAW (no GroupNorm in front: src0 / src1 when gn_scale is NULL, skip0 / skip1 always) are
@@ -107,6 +109,7 @@ typedef struct ddnm_conv_desc {
 } ddnm_conv_desc;
 
 #define DDNM_CONV_ONE_TILE 1
+#define DDNM_CONV_UPS_SUBPIXEL 2
 #define DDNM_AMAX_N 32   /* bound words per image (= the GroupNorm group count of both networks) */
 
 int ddnm_conv2d_f32(const ddnm_conv_desc* d, void* stream);
@@ -155,6 +158,16 @@ int ddnm_conv3x3_s16_persistent(const ddnm_conv_desc* d);   /* ABI 7 -- 1: the l
                                                                 workgroup per CU walks its tiles; same results bit for bit) */
 int64_t ddnm_conv3x3_s16_workspace_floats(const ddnm_conv_desc* d);
 int ddnm_conv3x3_s16_stats_tiles(const ddnm_conv_desc* d);
+/* Sub-pixel form of `nearest x2 -> 3x3` (ups = 1, flags & DDNM_CONV_UPS_SUBPIXEL; additions within ABI 7): output pixel
+ * (2y + py, 2x + px) = sum_{a,b in {0,1}} Wp[py][px][a][b] . X[y + py - 1 + a][x + px - 1 + b] on the low-resolution grid, with
+ * Wp = the 3x3 taps that land on the same source pixel, pre-summed: 16 tap products per source pixel instead of 36.
+ *   weight = split packing [4 Cout rows][4 steps (a, b)][Cin / 32][hi 32 | lo 32] of 2^s * Wp, row ((cb * 2 + py) * 2 + px) * 64 + c
+ *     for output channel cb * 64 + c; 2^s brings max|Wp| into [2^13, 2^14); acc_scale = 2^-s.
+ * 1 when the launch qualifies: low-resolution W % 32 == 0, H % 8 == 0, Cin % 32 == 0 (C0 too) with >= 2 chunks, Cout % 64 == 0,
+ * raw operand (amax_in required at launch), bias only (no badd / res / GroupNorm prologue / shortcut / NCHW), sizes addressable.
+ * Never splits K (workspace ignored); statistics: Ho * Wo / 256 partial rows per image.  A flagged launch that does not qualify
+ * is an error, never a fall-back. */
+int ddnm_conv3x3_s16_ups_subpixel_supported(const ddnm_conv_desc* d);
 float ddnm_conv3x3_s16_act_scale(void);   /* compile-time activation pre-scale: 1 since ABI 5 (the scale is per launch and
                                              image, derived on the device from ddnm_conv_desc::amax_in) */
 
