@@ -287,6 +287,7 @@ class Model(_net.GraphedNet):
         w["conv_out.bias"] = g("conv_out.bias")
         if self.split16:
             self._guard_normalised_operands(sd, w)
+            self._guard_weight_range(sd, w)
         half = self.ch // 2
         freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1)))   # models.py:16-17
         w["temb.freq"] = freq.to(dev)
@@ -318,6 +319,51 @@ class Model(_net.GraphedNet):
                 dropped.append(f"{a.name}.qkv")
         self.s16_dropped = dropped
         return dropped
+
+    def _guard_weight_range(self, sd, w):
+        """The split-fp16 kernels scale a launch's WEIGHTS by one power of two (ops.s16_weight_scale): a weight far below the
+        launch's maximum keeps an absolute error of 2^-25 in scaled units instead of 2^-22 of its own size.  Checked here per
+        launch, on the tensors that share an accumulator: an output row whose summed split error exceeds twice the all-relative
+        value (ops.s16_weight_row_bound > ops.S16_WEIGHT_ROW_LIMIT = 2^-21, derived there) would lose digits against the fp32
+        kernel, so the layer's split weights are dropped and it runs the exact-fp32 kernel.  Appends to `self.s16_dropped`."""
+        g = lambda k: sd[k + ".weight"].detach().to(device=self.device, dtype=torch.float32)  # noqa: E731
+
+        def over(key, *ws):
+            e = w.get(key)
+            return e is not None and ops.s16_weight_row_bound(e[1], *ws) > ops.S16_WEIGHT_ROW_LIMIT
+
+        def drop(name, *keys):
+            if any([w.pop(k, None) is not None for k in keys]) and name not in self.s16_dropped:
+                self.s16_dropped.append(name)
+        for rb in self.res_blocks:
+            n = rb.name
+            if over(n + ".conv1.s16", g(n + ".conv1")):
+                drop(n + ".conv1", n + ".conv1.s16")
+            if rb.cin != rb.cout:
+                # conv2 and its fused shortcut share an accumulator and a scale; the un-fused packing has its own
+                if over(n + ".conv2.s16", g(n + ".conv2"), g(n + ".nin_shortcut")):
+                    drop(n + ".conv2", n + ".conv2.s16", n + ".nin_shortcut.s16")
+                if over(n + ".nin_shortcut.s16", g(n + ".nin_shortcut")):
+                    drop(n + ".nin_shortcut", n + ".nin_shortcut.s16")
+            elif over(n + ".conv2.s16", g(n + ".conv2")):
+                drop(n + ".conv2", n + ".conv2.s16")
+        attns = [a for (_, at, _, _) in self.down for a in at] + [self.mid[1]] + [a for lvl in self.up for a in self.up[lvl][1]]
+        for a in attns:
+            n = a.name
+            if over(n + ".qkv.s16", torch.cat([g(f"{n}.{p}") for p in ("q", "k", "v")], 0)):
+                drop(n + ".qkv", n + ".qkv.s16")
+            if over(n + ".proj_out.s16", g(n + ".proj_out")):
+                drop(n + ".proj_out", n + ".proj_out.s16")
+        for lvl, (_, _, has_down, _) in enumerate(self.down):
+            n = f"down.{lvl}.downsample.conv"
+            if has_down and over(n + ".s16", g(n)):
+                drop(n, n + ".s16")
+        for lvl, (_, _, has_up, _) in self.up.items():
+            n = f"up.{lvl}.upsample.conv"
+            # the sub-pixel form splits the PHASE weights (sums of up to four taps, their own scale): judged on those
+            if has_up and (over(n + ".s16", g(n)) or over(n + ".s16_subpixel", ops.upsample_phase_weights(g(n)))):
+                drop(n, n + ".s16", n + ".s16_subpixel")
+        return self.s16_dropped
 
     # ------------------------------------------------------------------ forward
     def _max_gn_partials(self):

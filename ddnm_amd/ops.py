@@ -168,6 +168,35 @@ def s16_weight_scale(*ws):
     return 2.0 ** (13 - math.floor(math.log2(m)))
 
 
+def s16_weight_row_bound(scale, *ws):
+    """Worst output row's relative split error of a launch's weights: max_o sum_k eps(scale W[o, k]) / sum_k |scale W[o, k]|
+    over ALL tensors that share the accumulator (3x3 kernel + fused shortcut), with the element model of
+    csrc/conv_common.h::split_store: eps(v) = 0 for v = 0, 2^-25 for |v| < 0.25 (`lo` is a subnormal fp16 number), 2^-22 |v|
+    above.  Exactly 2^-22 while every weight of every row is carried relatively; it grows when a row lies so far below the
+    launch's maximum that its weights keep the ABSOLUTE 2^-25 only.  All-zero rows (Cout padding) are skipped.  A phase tensor
+    [py][px][O][I][a][b] (upsample_phase_weights) is judged per (phase, output channel): each phase has its own accumulator."""
+    num = den = None
+    for w in ws:
+        v = w.detach().to(torch.float64)
+        v = (v.flatten(0, 2) if v.dim() == 6 else v).flatten(1).abs() * float(scale)       # [rows][everything a row sums over]
+        eps = torch.where(v == 0, torch.zeros_like(v), torch.where(v < 0.25, torch.full_like(v, 2.0 ** -25), v * 2.0 ** -22))
+        n, d_ = eps.sum(1), v.sum(1)
+        num, den = (n, d_) if num is None else (num + n, den + d_)
+    live = den > 0
+    if not bool(live.any()):
+        return 0.0
+    return float((num[live] / den[live]).max())
+
+
+# Weight-range limit of the split-fp16 launches (Model.load_state_dict): a launch whose s16_weight_row_bound exceeds it runs
+# the exact-fp32 kernel.  In units of 2^-22 a product's relative error is (weight term) + (activation term: 1 for an operand
+# carried relatively) + (dropped lo.lo': 1); an all-relative weight row has weight term 1, and allowing it to DOUBLE -- 2^-21 --
+# keeps an output channel within 4 . 2^-22 of its own magnitude sum |w||a| (the row sum weighs every k alike, i.e. activations of
+# comparable size over k; the tier definition of tests/s16_model.py weighs them as they are), the order of the fp32 kernel's
+# own accumulation error.  Beyond it a row keeps only an absolute bound (relative to the launch's largest row).  Not tuned.
+S16_WEIGHT_ROW_LIMIT = 2.0 ** -21
+
+
 def pack_conv_weight_s16(w, scale):
     """OIHW fp32 -> the split packing of ddnm_conv3x3_s16_f32: (O, ky, kx, I) with Cout padded to 128, every 32-channel
     chunk stored as 32 hi halfs then 32 lo halfs of scale * W (hi = rn16, lo = rn16(residual)); returned as an fp16
