@@ -248,6 +248,9 @@ PROTOTYPES = {
     "ddnm_ssim_workspace_elems": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "ddnm_ssim_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
                                 c_int32, c_void_p]),
+    "ddnm_sample_stats_workspace_elems": (c_int64, [c_int32, c_int64]),
+    "ddnm_sample_stats_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -10,6 +10,9 @@
 // A second kernel adds the C * tiles partials of each image in a fixed order and divides.  No floating-point atomics:
 // an image's value depends on its own pixels only, bit for bit, wherever it sits in a batch.
 //
+// Sample statistics (ddnm_sample_stats_f32, below the SSIM): the per-pixel mean and standard deviation over the K
+// restorations of one measurement, and their per-image summaries, with the same no-atomics reduction.
+//
 // Why fp64 moments: in fp32 the variance w*x^2 - mu^2 of a flat region cancels to ~1e-7 absolute against C2 = 9e-4,
 // which moves the per-image value by 1e-4 (constant 0.3 vs 0.7; 0.9 vs 0.9 + 1e-3 * noise).  The product of two fp32
 // values is exact in fp64, so x^2, y^2 and xy carry no rounding at all and SSIM(x, x) is exactly 1.  The tile is 16 tall
@@ -122,6 +125,159 @@ __global__ __launch_bounds__(256) void ssim_finalize_kernel(const double* __rest
     if (threadIdx.x == 0) ssim[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) / count;
 }
 
+// ---------------------------------------------------------------- mean / standard deviation over K samples
+// One 256-thread workgroup per STATS_ELEMS consecutive elements of one image; thread t owns the four elements
+// 4 t .. 4 t + 3 of each 1024-element slab.  The vector path moves them as one 16-byte load per sample and one 16-byte
+// store per result, the scalar path element by element with a bound check -- the same elements in the same order on the
+// same thread, so both paths give the same bits.  Per element: v_k = clamp((x_k + 1) / 2, 0, 1) in fp32 (what
+// finalize_psnr_kernel forms), then two passes in fp64 -- m = sum(v_k) / K, s = sqrt(sum((v_k - m)^2) / (K - 1)) -- over
+// the K samples, re-read for the second pass (they are in cache: the thread just loaded them).  Deviations from the mean,
+// never sum(v^2) - sum(v)^2 / K, which loses every digit of a small variance on a large mean.
+constexpr int STATS_SLABS = 2;
+constexpr int STATS_ELEMS = STATS_SLABS * 1024;
+
+__device__ __forceinline__ float stats_unit(float v) {
+    return fminf(fmaxf((v + 1.0f) / 2.0f, 0.0f), 1.0f);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void sample_stats_kernel(const float* __restrict__ x, int64_t image_stride,
+                                                           int64_t sample_stride, const float* __restrict__ xo,
+                                                           float* __restrict__ mean_img, float* __restrict__ std_img,
+                                                           double* __restrict__ work, int K, int64_t chw, int nblk) {
+#pragma clang fp contract(off)
+    __shared__ double red[2][4];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk;
+    const float* xb = x + (int64_t)b * image_stride;
+    const int64_t ob = (int64_t)b * chw;
+    double acc_sse = 0.0, acc_std = 0.0;
+#pragma unroll
+    for (int slab = 0; slab < STATS_SLABS; ++slab) {
+        const int64_t e0 = (int64_t)blk * STATS_ELEMS + slab * 1024 + tid * 4;
+        if (e0 >= chw) continue;
+        const int n = VEC ? 4 : (int)(chw - e0 < 4 ? chw - e0 : 4);
+        double sum[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int k = 0; k < K; ++k) {
+            const float* p = xb + (int64_t)k * sample_stride + e0;
+            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (VEC) {
+                const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+                v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+            } else {
+                for (int j = 0; j < n; ++j) v[j] = p[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sum[j] += (double)stats_unit(v[j]);
+        }
+        double m[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[j] = sum[j] / (double)K;
+        if (K > 1) {
+            for (int k = 0; k < K; ++k) {
+                const float* p = xb + (int64_t)k * sample_stride + e0;
+                float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (VEC) {
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(p);
+                    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+                } else {
+                    for (int j = 0; j < n; ++j) v[j] = p[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const double d = (double)stats_unit(v[j]) - m[j];
+                    ss[j] += d * d;
+                }
+            }
+        }
+        float m32[4], s32[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double s = K > 1 ? sqrt(ss[j] / (double)(K - 1)) : 0.0;
+            m32[j] = (float)m[j];
+            s32[j] = (float)s;
+            if (j < n) acc_std += s;
+        }
+        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (xo) {
+            if (VEC) {
+                const f32x4 q = *reinterpret_cast<const f32x4*>(xo + ob + e0);
+                o[0] = q.x, o[1] = q.y, o[2] = q.z, o[3] = q.w;
+            } else {
+                for (int j = 0; j < n; ++j) o[j] = xo[ob + e0 + j];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float dd = m32[j] - stats_unit(o[j]);      // fp32, the convention of finalize_psnr_kernel
+                if (j < n) acc_sse += (double)(dd * dd);
+            }
+        }
+        if (VEC) {
+            f32x4 qm, qs;
+            qm.x = m32[0], qm.y = m32[1], qm.z = m32[2], qm.w = m32[3];
+            qs.x = s32[0], qs.y = s32[1], qs.z = s32[2], qs.w = s32[3];
+            *reinterpret_cast<f32x4*>(mean_img + ob + e0) = qm;
+            *reinterpret_cast<f32x4*>(std_img + ob + e0) = qs;
+        } else {
+            for (int j = 0; j < n; ++j) {
+                mean_img[ob + e0 + j] = m32[j];
+                std_img[ob + e0 + j] = s32[j];
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc_sse += __shfl_xor(acc_sse, o);
+        acc_std += __shfl_xor(acc_std, o);
+    }
+    if ((tid & 63) == 0) {
+        red[0][tid >> 6] = acc_sse;
+        red[1][tid >> 6] = acc_std;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        work[2 * (int64_t)blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        work[2 * (int64_t)blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
+}
+
+// sse_mean[b] = sum of the image's `n` squared-error partials, std_mean[b] = (sum of its std partials) / chw; the order
+// depends on n alone
+__global__ __launch_bounds__(256) void sample_stats_finalize_kernel(const double* __restrict__ work,
+                                                                    double* __restrict__ sse_mean,
+                                                                    double* __restrict__ std_mean, int n, double chw) {
+    __shared__ double red[2][4];
+    const double* w = work + 2 * (int64_t)blockIdx.x * n;
+    double a0 = 0.0, a1 = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        a0 += w[2 * i];
+        a1 += w[2 * i + 1];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a0 += __shfl_xor(a0, o);
+        a1 += __shfl_xor(a1, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = a0;
+        red[1][threadIdx.x >> 6] = a1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (sse_mean) sse_mean[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        std_mean[blockIdx.x] = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / chw;
+    }
+}
+
+// workgroups per image: a function of chw alone, so that an image's partials do not depend on the batch around it
+int64_t stats_blocks(int64_t chw) {
+    return (chw + STATS_ELEMS - 1) / STATS_ELEMS;
+}
+
+bool aligned16(const void* p) {
+    return ((uintptr_t)p & 15) == 0;
+}
+
 // g_i = exp(-(i-5)^2 / (2 * 1.5^2)) / sum, in fp64
 ssim_window ssim_make_window() {
     ssim_window win;
@@ -167,5 +323,36 @@ extern "C" int ddnm_ssim_f32(const float* x, const float* y, double* ssim, doubl
                 transform != 0, win);
     const double count = (double)C * (double)(H - (SSIM_WIN - 1)) * (double)(W - (SSIM_WIN - 1));
     DDNM_LAUNCH(ssim_finalize_kernel, dim3(B), dim3(256), 0, st, work, ssim, C * tiles, count);
+    return 0;
+}
+
+extern "C" int64_t ddnm_sample_stats_workspace_elems(int32_t B, int64_t chw) {
+    if (B < 1 || chw < 1) return DDNM_E_BADARG;
+    const int64_t nblk = stats_blocks(chw);
+    if (nblk > INT32_MAX || nblk * B > INT32_MAX) return DDNM_E_SHAPE;      // one workgroup per partial pair, 1-D grid
+    return 2 * nblk * B;
+}
+
+extern "C" int ddnm_sample_stats_f32(const float* x, int64_t image_stride, int64_t sample_stride, const float* x_orig,
+                                     float* mean_img, float* std_img, double* sse_mean, double* std_mean, double* work,
+                                     int64_t work_elems, int32_t B, int32_t K, int64_t chw, void* stream) {
+    if (!x || !mean_img || !std_img || !std_mean || !work || B < 1 || K < 1 || chw < 1) return DDNM_E_BADARG;
+    if ((x_orig != nullptr) != (sse_mean != nullptr)) return DDNM_E_BADARG;
+    if (image_stride < 0 || sample_stride < 0) return DDNM_E_BADARG;
+    const int64_t need = ddnm_sample_stats_workspace_elems(B, chw);
+    if (need < 0) return (int)need;
+    if (work_elems < need) return DDNM_E_SHAPE;
+    const int nblk = (int)stats_blocks(chw);
+    const bool vec = chw % 4 == 0 && image_stride % 4 == 0 && sample_stride % 4 == 0 && aligned16(x) &&
+                     aligned16(x_orig) && aligned16(mean_img) && aligned16(std_img);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(need / 2));
+    if (vec)
+        DDNM_LAUNCH(sample_stats_kernel<true>, grid, dim3(256), 0, st, x, image_stride, sample_stride, x_orig, mean_img,
+                    std_img, work, K, chw, nblk);
+    else
+        DDNM_LAUNCH(sample_stats_kernel<false>, grid, dim3(256), 0, st, x, image_stride, sample_stride, x_orig, mean_img,
+                    std_img, work, K, chw, nblk);
+    DDNM_LAUNCH(sample_stats_finalize_kernel, dim3(B), dim3(256), 0, st, work, sse_mean, std_mean, nblk, (double)chw);
     return 0;
 }

@@ -1,9 +1,10 @@
-"""PSNR and SSIM of an image folder the runner wrote: `python -m ddnm_amd.evaluate <image_folder> [--against restored|Apy]
-[--json FILE]`.
+"""PSNR and SSIM of an image folder the runner wrote: `python -m ddnm_amd.evaluate <image_folder>
+[--against restored|Apy|mean] [--sample k] [--json FILE]`.
 
-`restored` (default) pairs `Apy/orig_{i}.png` with the restoration `{i}_0.png`; `Apy` pairs it with `Apy/Apy_{i}.png`,
-the A^+ y baseline row of the paper's tables.  The 8-bit PNGs are loaded with PIL and evaluated on the GPU by the
-kernels the runner reports with: PSNR by `ops.finalize_psnr` on 2v - 1, SSIM by `ops.ssim(..., transform=False)`.
+`restored` (default) pairs `Apy/orig_{i}.png` with the restoration `{i}_0.png` -- `{i}_{k}.png` with `--sample k`, the
+k-th restoration of a DDNM_SAMPLES run; `Apy` pairs it with `Apy/Apy_{i}.png`, the A^+ y baseline row of the paper's
+tables; `mean` pairs it with `mean/mean_{i}.png`, the posterior mean of a DDNM_SAMPLES run.  The 8-bit PNGs are loaded
+with PIL and evaluated on the GPU by the kernels the runner reports with: PSNR by `ops.finalize_psnr` on 2v - 1, SSIM by `ops.ssim(..., transform=False)`.
 One `index PSNR SSIM` row per image, then the averages.  Indices present on one side only are listed and skipped.
 
 (`--simplified` runs name the restoration of image i `{i - 1}_0.png`, like the reference; rename them before pairing.)
@@ -16,7 +17,7 @@ import sys
 
 import numpy as np
 
-AGAINST = ("restored", "Apy")
+AGAINST = ("restored", "Apy", "mean")
 BATCH = 32          # images of one size evaluated per launch
 
 
@@ -32,18 +33,28 @@ def _indexed(folder, pattern):
     return found
 
 
-def pair_files(image_folder, against="restored"):
+def pair_files(image_folder, against="restored", sample=0):
     """(pairs, missing): pairs = [(i, path of orig_i, path of the image compared with it)] sorted by i; missing =
-    {"orig": [...], against: [...]} = the indices that have the other file only.  Touches file names only."""
+    {"orig": [...], against: [...]} = the indices that have the other file only.  `sample` picks the restoration
+    `{i}_{sample}.png` of a DDNM_SAMPLES run (against="restored" only).  Touches file names only."""
     if against not in AGAINST:
         raise ValueError(f"--against: unknown choice {against!r}; accepted values: {', '.join(AGAINST)}")
+    sample = int(sample)
+    if sample < 0 or (sample and against != "restored"):
+        raise ValueError(f"--sample {sample}: a sample index >= 0, with --against restored only")
     apy = os.path.join(image_folder, "Apy")
     orig = _indexed(apy, r"orig_(\d+)\.png")
-    other = _indexed(image_folder, r"(\d+)_0\.png") if against == "restored" else _indexed(apy, r"Apy_(\d+)\.png")
+    if against == "restored":
+        other = _indexed(image_folder, r"(\d+)_%d\.png" % sample)
+    elif against == "mean":
+        other = _indexed(os.path.join(image_folder, "mean"), r"mean_(\d+)\.png")
+    else:
+        other = _indexed(apy, r"Apy_(\d+)\.png")
     pairs = [(i, orig[i], other[i]) for i in sorted(orig.keys() & other.keys())]
     missing = {"orig": sorted(other.keys() - orig.keys()), against: sorted(orig.keys() - other.keys())}
     if not pairs:
-        raise FileNotFoundError(f"{image_folder}: no Apy/orig_<i>.png has a partner for --against {against}")
+        raise FileNotFoundError(f"{image_folder}: no Apy/orig_<i>.png has a partner for --against {against}" +
+                                (f" --sample {sample}" if sample else ""))
     return pairs, missing
 
 
@@ -83,9 +94,11 @@ def main(argv=None):
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("image_folder", help="<exp>/image_samples/<-i> of a finished run")
     ap.add_argument("--against", choices=AGAINST, default="restored", help="what Apy/orig_<i>.png is compared with")
+    ap.add_argument("--sample", type=int, default=0, metavar="k",
+                    help="with --against restored: compare the k-th restoration <i>_<k>.png of a DDNM_SAMPLES run")
     ap.add_argument("--json", metavar="FILE", help="also write the rows and averages as JSON")
     args = ap.parse_args(argv)
-    pairs, missing = pair_files(args.image_folder, args.against)
+    pairs, missing = pair_files(args.image_folder, args.against, args.sample)
     for side, idx in missing.items():
         if idx:
             print(f"skipped (no {side} file): {' '.join(map(str, idx))}")

@@ -22,7 +22,11 @@ Deliberate differences at the boundary (not in the results):
     one mask per run; a 2-D file behaves as there;
   * DDNM_METRICS=ssim adds the SSIM column of the paper's tables: an `SSIM: %.4f` line (running mean) after every
     `PSNR:` line and `Total Average SSIM: %.4f` after the total (ops.ssim, csrc/metrics.hip).  Unset, nothing changes.
-    The averages and, with the switch, this rank's per-image values stay on the runner as `last_metrics`.
+    The averages and, with the switch, this rank's per-image values stay on the runner as `last_metrics`;
+  * DDNM_SAMPLES=K (default 1) restores every measurement K times in ONE sampler call, sample k with the noise of a run
+    under `--seed seed + k` (sample_sources) and all K with the one measurement y of the run's own seed: `{i}_{k}.png` for
+    every k (the reference hard-wires the 0), `mean/mean_{i}.png` (the posterior mean) and `std/std_{i}.png` (the
+    per-pixel standard deviation, ops.sample_stats, csrc/metrics.hip).  The PSNR / SSIM lines stay those of sample 0.
 """
 import os
 import random
@@ -258,6 +262,42 @@ def fuse_batches():
     return k
 
 
+# DDNM_SAMPLES=K: K restorations of every measurement in ONE sampler call (default 1 = off)
+def samples():
+    k = int(os.environ.get("DDNM_SAMPLES", "1"))
+    if k < 1:
+        raise ValueError(f"DDNM_SAMPLES must be >= 1, got {k}")
+    return k
+
+
+def check_samples(k, simplified):
+    """What a run with DDNM_SAMPLES=k cannot do, said before its first image is loaded."""
+    if k > 1 and simplified:
+        raise ValueError(f"DDNM_SAMPLES={k} needs the SVD path: the --simplified loop draws its noise from ATen's global "
+                         "generator, which has no per-sample key")
+
+
+def sample_sources(seed, bi, k, lo):
+    """Philox sources of the `k` samples of loader batch `bi` for a rank whose slice of the batch starts at image `lo`:
+    sample s draws what the batch draws in a run under `--seed seed + s` (sample 0: today's source)."""
+    return [ops.PhiloxNoise(_mix64(seed + s, bi), image_base=lo) for s in range(k)]
+
+
+def sample_rows(images, sizes, k):
+    """Image of every row of a sampler call over `k` samples: `images` lists the call's images batch after batch,
+    `sizes` the number of images of each batch; the rows run batch-major, then sample, then image."""
+    if sum(sizes) != len(images):
+        raise ValueError(f"sample_rows: {len(images)} images for batches of {list(sizes)}")
+    rows, off = [], 0
+    for n in sizes:
+        rows += list(images[off:off + n]) * k
+        off += n
+    return rows
+
+
+STD_DISPLAY_GAIN = 4.0      # std/std_{i}.png holds clamp(gain * s, 0, 1): a display choice, s itself rarely exceeds 0.25
+
+
 # DDNM_METRICS: comma-separated metrics reported NEXT TO the PSNR (unset / empty = PSNR alone, today's output)
 METRICS = ("ssim",)
 SSIM_MIN_SIZE = 11          # the 11x11 window needs one valid position
@@ -282,10 +322,13 @@ class MetricLog:
     of `Apy/orig_{i}.png`); the simplified runner writes that image's restoration as `{i - 1}_0.png`, like the
     reference."""
 
-    def __init__(self, image_size):
+    def __init__(self, image_size, samples=1):
         self.with_ssim = "ssim" in extra_metrics(image_size)
         self.psnr_sum, self.ssim_sum, self.n = 0.0, 0.0, 0
         self.index, self.psnr, self.ssim = [], [], []
+        # DDNM_SAMPLES=K > 1: the posterior-mean image, all K samples, the mean standard deviation (add_samples)
+        self.samples = samples
+        self.mean_psnr_sum, self.all_psnr_sum, self.std_sum, self.mean_ssim_sum = 0.0, 0.0, 0.0, 0.0
 
     def add(self, x, x_orig, psnr, idx0):
         """One finished loader batch: x, x_orig on the [-1, 1] scale, `psnr` from ops.finalize_psnr; prints the lines."""
@@ -301,18 +344,54 @@ class MetricLog:
             self.ssim += s.cpu().tolist()
             print("SSIM: %.4f" % (self.ssim_sum / self.n))
 
+    def add_samples(self, psnr_mean, psnr_all, std_mean, mean_img, x_orig):
+        """The K-sample figures of the loader batch `add` has just counted (sample 0): `psnr_mean`, `std_mean` [b] and
+        `mean_img` ([0, 1] scale) from ops.sample_stats, `psnr_all` [K, b] of every sample, x_orig on the [-1, 1] scale."""
+        self.mean_psnr_sum += float(psnr_mean.sum())
+        self.all_psnr_sum += float(psnr_all.double().sum())
+        self.std_sum += float(std_mean.sum())
+        print("Mean-of-K PSNR: %.2f" % (self.mean_psnr_sum / self.n))
+        print("Sample PSNR: %.2f" % (self.all_psnr_sum / (self.n * self.samples)))
+        print("Std: %.4f" % (self.std_sum / self.n))
+        if self.with_ssim:
+            self.mean_ssim_sum += float(ops.ssim(mean_img, ops.finalize_psnr(x_orig)[0], transform=False).sum())
+            print("Mean-of-K SSIM: %.4f" % (self.mean_ssim_sum / self.n))
+
     def total(self, rank, device, reduce):
         """Totals over the ranks (`reduce`: the sums live on several ranks) printed by rank 0; returns last_metrics."""
         if reduce:
             self.psnr_sum, self.n = ddist.reduce_sum(self.psnr_sum, device), int(ddist.reduce_sum(self.n, device))
             if self.with_ssim:
                 self.ssim_sum = ddist.reduce_sum(self.ssim_sum, device)
+            if self.samples > 1:
+                self.mean_psnr_sum = ddist.reduce_sum(self.mean_psnr_sum, device)
+                self.all_psnr_sum = ddist.reduce_sum(self.all_psnr_sum, device)
+                self.std_sum = ddist.reduce_sum(self.std_sum, device)
+                if self.with_ssim:
+                    self.mean_ssim_sum = ddist.reduce_sum(self.mean_ssim_sum, device)
         n = max(self.n, 1)
         if rank == 0:
             print("Total Average PSNR: %.2f" % (self.psnr_sum / n))
             if self.with_ssim:
                 print("Total Average SSIM: %.4f" % (self.ssim_sum / n))
+            if self.samples > 1:
+                print("Total Average Mean-of-K PSNR: %.2f" % (self.mean_psnr_sum / n))
+                print("Total Average Sample PSNR: %.2f" % (self.all_psnr_sum / (n * self.samples)))
+                print("Total Average Std: %.4f" % (self.std_sum / n))
+                if self.with_ssim:
+                    print("Total Average Mean-of-K SSIM: %.4f" % (self.mean_ssim_sum / n))
             print("Number of samples: %d" % self.n)
+            if self.samples > 1:
+                print("Samples per image: %d" % self.samples)
+        extra = {}
+        if self.samples > 1:
+            extra = {"samples": self.samples, "psnr_mean_image": self.mean_psnr_sum / n,
+                     "psnr_all_samples": self.all_psnr_sum / (n * self.samples), "std": self.std_sum / n}
+            if self.with_ssim:
+                extra["ssim_mean_image"] = self.mean_ssim_sum / n
+        return {**self._totals(n), **extra}
+
+    def _totals(self, n):
         return {"psnr": self.psnr_sum / n, "ssim": self.ssim_sum / n if self.with_ssim else None, "n": self.n,
                 "index": self.index if self.with_ssim else None, "psnr_per_image": self.psnr if self.with_ssim else None,
                 "ssim_per_image": self.ssim if self.with_ssim else None}
@@ -429,6 +508,7 @@ class Diffusion(object):
         raise ValueError(cfg.model.type)
 
     def sample(self, simplified):
+        check_samples(samples(), simplified)
         model = self._build_model()
         # batch sizes of 1 and 2 (the reference's shipped `sampling.batch_size: 1`) replay the forward from a hipGraph:
         # eager, the host needs longer to enqueue a forward's ~250-300 launches than the GPU to run them
@@ -510,8 +590,14 @@ class Diffusion(object):
         print(f"Start from {args.subset_start}")
         idx_so_far = args.subset_start
         C, S = config.data.channels, config.data.image_size
-        log = MetricLog(S)
+        # DDNM_SAMPLES=NS: every measurement restored NS times in one sampler call, rows [sample k][image j], sample k with
+        # the noise of a run under --seed seed + k and all of them with the one y of this run
+        NS = samples()
+        log = MetricLog(S, NS)
         os.makedirs(os.path.join(args.image_folder, "Apy"), exist_ok=True)      # (rank 0 made the image folder before the first barrier)
+        if NS > 1:
+            os.makedirs(os.path.join(args.image_folder, "mean"), exist_ok=True)
+            os.makedirs(os.path.join(args.image_folder, "std"), exist_ok=True)
         # Sharding (one process per GPU): a loader batch of at least `world` images is split by image index and gathered once;
         # SMALLER batches -- every shipped config has sampling.batch_size 1 -- are dealt whole, round-robin, each rank writing
         # its own images (file names carry the global image index) and the PSNR reduced at the end (splitting a
@@ -542,9 +628,33 @@ class Diffusion(object):
                 save_image(img[j], os.path.join(args.image_folder, f"{idx0 + j}_{0}.png"))
             log.add(x_all, x_orig, psnr, idx0)
 
-        def restore(x, y_loc, classes, noise, A_funcs):
-            if bank is not None and A_funcs.rows != [i % len(bank) for i in next(calls)]:
-                raise RuntimeError("sampler call and restored_images disagree about the images of this call")
+        def finish_samples(x_rows, layout, x_orig, idx0):
+            """The NS * b restorations of one loader batch ("samples_major": [k][j] as the sampler leaves them,
+            "images_major": [j][k] after the gather): every sample's PNG, sample 0's lines, then the K-sample figures."""
+            b = x_orig.shape[0]
+            x_rows = x_rows.contiguous()
+            xs = x_rows.view(NS, b, C, S, S) if layout == "samples_major" else x_rows.view(b, NS, C, S, S).transpose(0, 1)
+            psnr_all = []
+            for k in range(NS):
+                x_k = xs[k].contiguous()
+                img, psnr = ops.finalize_psnr(x_k, x_orig)
+                for j in range(b):
+                    save_image(img[j], os.path.join(args.image_folder, f"{idx0 + j}_{k}.png"))
+                if k == 0:
+                    log.add(x_k, x_orig, psnr, idx0)
+                psnr_all.append(psnr)
+            mean_img, std_img, psnr_mean, std_mean = ops.sample_stats(x_rows, b, NS, layout, x_orig)
+            std_shown = (std_img * STD_DISPLAY_GAIN).clamp_(0.0, 1.0)
+            for j in range(b):
+                save_image(mean_img[j], os.path.join(args.image_folder, f"mean/mean_{idx0 + j}.png"))
+                save_image(std_shown[j], os.path.join(args.image_folder, f"std/std_{idx0 + j}.png"))
+            log.add_samples(psnr_mean, torch.stack(psnr_all), std_mean, mean_img, x_orig)
+
+        def restore(x, y_loc, classes, noise, A_funcs, sizes=None):
+            if bank is not None:
+                images = next(calls)
+                if A_funcs.rows != [i % len(bank) for i in sample_rows(images, sizes or [len(images)], NS)]:
+                    raise RuntimeError("sampler call and restored_images disagree about the images of this call")
             with torch.no_grad():
                 if sigma_y == 0.0:       # noise-free case, DDNM (diffusion.py:587-588)
                     xs, _ = ddnm_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, cls_fn=cls_fn,
@@ -568,9 +678,19 @@ class Diffusion(object):
                 # (element, iteration, image index in the batch); bench.py times this path
                 noise = ops.PhiloxNoise(_mix64(args.seed, bi), image_base=lo)
                 x = noise.tensor(ops.PhiloxNoise.XT_ITER, torch.empty(max(hi - lo, 1), C, S, S, device=self.device))[:hi - lo]
+                parts = [(noise, j) for j in range(hi - lo)]      # (source, image) of every row, for a keyed call
+                if NS > 1:
+                    srcs = sample_sources(args.seed, bi, NS, lo)
+                    like = torch.empty(max(hi - lo, 1), C, S, S, device=self.device)
+                    x = torch.cat([src.tensor(ops.PhiloxNoise.XT_ITER, like)[:hi - lo] for src in srcs], 0)
+                    parts = [(src, j) for src in srcs for j in range(hi - lo)]
             else:
                 noise = BatchNoise(args.seed, bi, b, (C, S, S), lo, hi, self.device)
                 x = noise.x_T()
+                parts = [noise]                                   # the tapes of a fused call, one per sample
+                if NS > 1:
+                    parts += [BatchNoise(args.seed + k, bi, b, (C, S, S), lo, hi, self.device) for k in range(1, NS)]
+                    x = torch.cat([x] + [t.x_T() for t in parts[1:]], 0)
             if bank is not None:
                 A_funcs = bank.for_images(range(idx_so_far, idx_so_far + b))
             y = A_funcs.A(x_orig)                # the whole batch: operators are cheap, and the writer needs A^+ y of all
@@ -579,6 +699,8 @@ class Diffusion(object):
                     y = y + measurement_noise(_mix64(args.seed, bi) ^ 0x5DEECE66D, y.reshape(b, -1)).reshape(y.shape) * sigma_y
                 else:
                     y = y + noise.draw(tuple(y.shape)) * sigma_y
+                    for t in parts[1:]:
+                        t.draw(tuple(y.shape))       # the samples share y; each tape still moves as in its own run
             if writer:
                 Apy = A_funcs.A_pinv(y).view(b, C, S, S)
                 if args.deg[:6] == "deblur":
@@ -594,21 +716,48 @@ class Diffusion(object):
                                os.path.join(args.image_folder, f"Apy/orig_{idx_so_far + i}.png"))
             if fuse:
                 # whole batches (lo, hi = 0, b): held until the last batch of the group, restored together
-                pending.append((x, y.reshape(b, -1).contiguous(), classes, noise, x_orig, idx_so_far, A_funcs))
+                if NS > 1 and bank is not None:
+                    A_funcs = bank.for_images(list(range(idx_so_far, idx_so_far + b)) * NS)
+                y_rows = y.reshape(b, -1).contiguous()
+                pending.append((x, y_rows.repeat(NS, 1) if NS > 1 else y_rows, classes.repeat(NS) if NS > 1 else classes,
+                                parts, x_orig, idx_so_far, A_funcs))
                 if bi in group_ends:
                     if philox:
-                        fnoise = ops.KeyedPhiloxNoise.from_sources([(p[3], j) for p in pending for j in range(p[4].shape[0])])
+                        fnoise = ops.KeyedPhiloxNoise.from_sources([pair for p in pending for pair in p[3]])
                     else:
-                        fnoise = FusedTape([p[3] for p in pending])
+                        fnoise = FusedTape([t for p in pending for t in p[3]])
                     x_fused = restore(torch.cat([p[0] for p in pending], 0), torch.cat([p[1] for p in pending], 0),
                                       torch.cat([p[2] for p in pending], 0), fnoise,
-                                      A_funcs if bank is None else PerImageInpainting.concat([p[6] for p in pending]))
+                                      A_funcs if bank is None else PerImageInpainting.concat([p[6] for p in pending]),
+                                      [p[4].shape[0] for p in pending])
                     off = 0
                     for p in pending:                # one PSNR line per loader batch, in loader order
                         nb = p[4].shape[0]
-                        finish(x_fused[off:off + nb], p[4], p[5])
-                        off += nb
+                        if NS > 1:
+                            finish_samples(x_fused[off:off + NS * nb], "samples_major", p[4], p[5])
+                        else:
+                            finish(x_fused[off:off + nb], p[4], p[5])
+                        off += NS * nb
                     pending = []
+                idx_so_far += b
+                continue
+            if NS > 1:
+                if hi > lo:
+                    x_loc = restore(x, y.reshape(b, -1)[lo:hi].repeat(NS, 1).contiguous(), classes.repeat(NS),
+                                    ops.KeyedPhiloxNoise.from_sources(parts) if philox else FusedTape(parts),
+                                    A_funcs if bank is None else
+                                    bank.for_images(list(range(idx_so_far + lo, idx_so_far + hi)) * NS))
+                else:
+                    x_loc = x                # empty shard: takes part in the gather only
+                if deal or world == 1:
+                    x_all, layout = x_loc, "samples_major"
+                else:
+                    # [k][j] -> one row of K * chw per image, so that the batch still meets in ONE collective; rank 0
+                    # holds [b][K][chw]
+                    rows = x_loc.reshape(NS, hi - lo, C * S * S).transpose(0, 1).reshape(hi - lo, NS * C * S * S)
+                    x_all, layout = ddist.gather_images(rows, n_total=b).reshape(b * NS, C, S, S), "images_major"
+                if writer:
+                    finish_samples(x_all, layout, x_orig, idx_so_far)
                 idx_so_far += b
                 continue
             if hi > lo:

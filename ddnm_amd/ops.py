@@ -1092,3 +1092,43 @@ def ssim(x, x_orig, transform=True):
     check(lib.ddnm_ssim_f32(_p(_f32c(x, "x")), _p(_f32c(x_orig, "x_orig")), _p(out), _p(work), n, B, C, H, W,
                             1 if transform else 0, _stream()), "ddnm_ssim_f32")
     return out
+
+
+SAMPLE_LAYOUTS = ("samples_major", "images_major")
+
+
+def sample_stats(x, n_images, n_samples, layout="samples_major", x_orig=None):
+    """Per-pixel mean and standard deviation over the `n_samples` restorations of each of `n_images` images
+    (csrc/metrics.hip::ddnm_sample_stats_f32).  `x` holds n_images * n_samples rows on the sampler's [-1, 1] scale:
+    "samples_major" is [sample k][image j] (what a sampler call over K samples returns), "images_major" is
+    [image j][sample k] (what rank 0 holds after the gather).  Returns (mean_img, std_img, psnr_mean, std_mean):
+    the two [n_images, ...] fp32 images on the [0, 1] scale, the PSNR of mean_img against `x_orig` ([-1, 1] scale; None
+    without it) as `finalize_psnr` computes it, and the per-image mean of the standard deviation, both float64
+    [n_images]."""
+    B, K = int(n_images), int(n_samples)
+    if layout not in SAMPLE_LAYOUTS:
+        raise ValueError(f"sample_stats: unknown layout {layout!r}; accepted values: {', '.join(SAMPLE_LAYOUTS)}")
+    if B < 1 or K < 1:
+        raise ValueError(f"sample_stats: need at least one image and one sample, got {B} images and {K} samples")
+    if x.dim() < 2 or x.shape[0] != B * K:
+        raise ValueError(f"sample_stats: x has {x.shape[0] if x.dim() else 0} rows, expected {B} images x {K} samples")
+    chw = x.numel() // (B * K)
+    if x_orig is not None and (x_orig.shape[0] != B or x_orig.numel() != B * chw):
+        raise ValueError(f"sample_stats: x_orig is {tuple(x_orig.shape)}, expected {B} images of {chw} values")
+    strides = (chw, B * chw) if layout == "samples_major" else (K * chw, chw)
+    lib = _lib.lib()
+    n = lib.ddnm_sample_stats_workspace_elems(B, chw)
+    if n < 0:
+        check(int(n), "ddnm_sample_stats_workspace_elems")
+    shape = (B,) + tuple(x.shape[1:])
+    mean_img = torch.empty(shape, dtype=torch.float32, device=x.device)
+    std_img = torch.empty(shape, dtype=torch.float32, device=x.device)
+    work = torch.empty(n, dtype=torch.float64, device=x.device)
+    std_mean = torch.empty(B, dtype=torch.float64, device=x.device)
+    sse = torch.empty(B, dtype=torch.float64, device=x.device) if x_orig is not None else None
+    check(lib.ddnm_sample_stats_f32(_p(_f32c(x, "x")), strides[0], strides[1],
+                                    _p(_f32c(x_orig, "x_orig")) if x_orig is not None else None, _p(mean_img),
+                                    _p(std_img), _p(sse), _p(std_mean), _p(work), n, B, K, chw, _stream()),
+          "ddnm_sample_stats_f32")
+    psnr = 10.0 * torch.log10(1.0 / (sse / chw)) if sse is not None else None
+    return mean_img, std_img, psnr, std_mean

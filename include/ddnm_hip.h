@@ -691,6 +691,27 @@ int64_t ddnm_ssim_workspace_elems(int32_t B, int32_t C, int32_t H, int32_t W);
 int ddnm_ssim_f32(const float* x, const float* y, double* ssim /* [B] */, double* work, int64_t work_elems, int32_t B,
                   int32_t C, int32_t H, int32_t W, int32_t transform, void* stream);
 
+/* Per-pixel mean and standard deviation over the K restorations (samples) of each of B images, with their per-image
+ * summaries.  Sample k of image b starts at x + b*image_stride + k*sample_stride (strides in floats): [K][B][chw] as a
+ * sampler call leaves it is (chw, B*chw), [B][K][chw] after a gather is (K*chw, chw).  Per element:
+ *   v_k = clamp((x_k+1)/2, 0, 1) in fp32 (what ddnm_finalize_psnr_f32 forms), m = sum_k v_k / K,
+ *   s = sqrt(sum_k (v_k - m)^2 / (K - 1)), s = 0 for K = 1,
+ * both moments in fp64 from deviations (two passes over the samples); only mean_img = (float)m and std_img = (float)s are
+ * rounded.  Per image: sse_mean[b] = sum_e (double)(d*d) with d = mean_img - clamp((x_orig+1)/2, 0, 1) in fp32 (K = 1
+ * gives ddnm_finalize_psnr_f32's img and sse); std_mean[b] = (sum_e s) / chw with the fp64 s.  The per-workgroup
+ * partials go to `work` and are added in an order that depends on chw alone, without atomics: an image's four outputs are
+ * bit for bit the same alone and at any position of any batch.  16-byte loads and stores when chw, both strides and
+ * the pointers allow, element-wise otherwise (same bits).  work: ddnm_sample_stats_workspace_elems(B, chw) doubles
+ * (= 2 * B * ceil(chw / 2048)), not read after the call.
+ * NULL x / mean_img / std_img / std_mean / work, B, K or chw < 1, a negative stride, or x_orig and sse_mean not both
+ * given or both NULL: DDNM_E_BADARG; more than 2^31-1 workgroups or work_elems below the query: DDNM_E_SHAPE (the query
+ * returns the same negative codes). */
+int64_t ddnm_sample_stats_workspace_elems(int32_t B, int64_t chw);
+int ddnm_sample_stats_f32(const float* x, int64_t image_stride, int64_t sample_stride, const float* x_orig /* [B][chw] or NULL */,
+                          float* mean_img /* [B][chw] */, float* std_img /* [B][chw] */,
+                          double* sse_mean /* [B], NULL iff x_orig NULL */, double* std_mean /* [B] */, double* work,
+                          int64_t work_elems, int32_t B, int32_t K, int64_t chw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
