@@ -157,51 +157,29 @@ extern "C" int ddnm_conv1x1_f16_supported(const ddnm_conv_desc* d) {
 extern "C" int64_t ddnm_conv1x1_f16_workspace_floats(const ddnm_conv_desc* d) {
     Plan1x1 pl;
     if (!d || !plan_1x1(d, &pl)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
+    return conv_slab_floats(d, pl.ksplit);
 }
 
 extern "C" int ddnm_conv1x1_f16_stats_tiles(const ddnm_conv_desc* d) {
     Plan1x1 pl;
     if (!d || !plan_1x1(d, &pl)) return DDNM_E_SHAPE;
     if (pl.fold) return 0;
-    return pl.ksplit > 1 ? splitk_stats_tiles(d) : d->Ho * d->Wo / 256;
+    return conv_stats_tiles(d, pl.ksplit, 256);
 }
 
 extern "C" int ddnm_conv1x1_f16_f32(const ddnm_conv_desc* d, void* stream) {
-    if (!d || !d->src0 || !d->weight || !d->out) return DDNM_E_BADARG;
-    if (d->B <= 0 || d->Cout <= 0 || d->Ho <= 0 || d->Wo <= 0) return DDNM_E_BADARG;
-    if (!conv_sizes_addressable(d)) return DDNM_E_SHAPE;
-    if (d->C1 > 0 && !d->src1) return DDNM_E_BADARG;
+    if (int e = conv_check_desc(d)) return e;
     Plan1x1 pl;
     if (!plan_1x1(d, &pl)) return DDNM_E_SHAPE;
     if (pl.fold && d->stats_out) return DDNM_E_SHAPE;
-    if (pl.ksplit > 1) {
-        const int64_t need = (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout;
-        if (!d->workspace || d->workspace_floats < need) {
-            if (d->stats_out) return DDNM_E_BADARG;
-            pl.ksplit = 1;
-        }
-    }
-    ConvArgs p;
-    p.d = *d;
+    if ((pl.ksplit = conv_run_ksplit(d, pl.ksplit)) < 0) return pl.ksplit;
+    ddnm_conv_desc f = *d;              // the descriptor the kernel sees
     if (pl.fold) {                      // pixels of all images as one flat strip
-        p.d.Ho = 1;
-        p.d.Wo = d->B * d->Ho * d->Wo;
-        p.d.Hin = 1;
-        p.d.Win = p.d.Wo;
-        p.d.B = 1;
+        f.Ho = f.Hin = 1;
+        f.Wo = f.Win = d->B * d->Ho * d->Wo;
+        f.B = 1;
     }
-    p.Cin = d->C0 + d->C1;
-    p.ntaps = 1;
-    p.Hs = p.d.Hin;
-    p.Ws = p.d.Win;
-    p.m_tiles = p.d.B * (p.d.Ho * p.d.Wo / 256);
-    p.n_tiles = d->Cout / 128;
-    p.TW = 256;
-    p.TW_log2 = 8;
-    p.tiles_x = 0;                      // flat strips of 256 pixels
-    p.ksplit = pl.ksplit;
-    p.ws = d->workspace;
+    const ConvArgs p = conv_args(f, 256, d->Cout / 128, 256, 8, 0, 1, pl.ksplit);      // tiles_x = 0: flat strips of 256 pixels
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(p.m_tiles * p.n_tiles, pl.ksplit);
     if (d->src_f16) { DDNM_LAUNCH(conv1x1_f16_kernel<true>, grid, dim3(512), 0, s, p); }

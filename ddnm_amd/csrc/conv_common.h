@@ -16,16 +16,20 @@ struct ConvArgs {
 // weights) through raw buffer descriptors with 32-bit BYTE sizes: every tensor of a launch must stay below 2^31 elements
 // (output side) resp. 2 GiB (operand side; the out-of-range sentinel 0x80000000 fetches the zero padding).  Larger
 // launches are refused (split the batch on the host) instead of wrapping around silently.
+// The operand side alone (both sources; `src_f16`: 2-byte elements): the plans of the buffer-addressed loaders
+// (plan_f16, plan_gs) ask this on their own, because the planning queries run without the launchers' checks.
+static inline bool conv_operand_offsets_fit(const ddnm_conv_desc* d) {
+    const int64_t px = (int64_t)d->B * (d->ups ? d->Hin / 2 : d->Hin) * (d->ups ? d->Win / 2 : d->Win);
+    const int64_t cmax = d->C0 > d->C1 ? d->C0 : d->C1;
+    return px * cmax * (d->src_f16 ? 2 : 4) < (int64_t)1 << 31;
+}
 static inline bool conv_sizes_addressable(const ddnm_conv_desc* d) {
     const int64_t lim = (int64_t)1 << 31;
     const int64_t out_el = (int64_t)d->B * d->Ho * d->Wo * d->Cout;
-    const int64_t hs = d->ups ? d->Hin / 2 : d->Hin, ws = d->ups ? d->Win / 2 : d->Win;
-    const int64_t cmax = d->C0 > d->C1 ? d->C0 : d->C1;
-    const int64_t src_b = (int64_t)d->B * hs * ws * cmax * (d->src_f16 ? 2 : 4);
     const int64_t cout_pad = ((int64_t)d->Cout + 127) / 128 * 128;
     const int64_t w_b = cout_pad * d->ksize * d->ksize * ((int64_t)d->C0 + d->C1) * 4;      // fp32 / split packing; fp16 is half
     const int64_t sk_el = (int64_t)d->B * d->Ho * d->Wo * (d->SC0 > d->SC1 ? d->SC0 : d->SC1);
-    return out_el < lim && src_b < lim && w_b < lim && sk_el < lim;
+    return out_el < lim && conv_operand_offsets_fit(d) && w_b < lim && sk_el < lim;
 }
 
 // persistent form of the split-fp16 3x3 kernel (conv_s16_persist.hip), dispatched from conv_igemm_f16.hip::run_f16
@@ -377,3 +381,63 @@ static inline int launch_splitk_reduce(const ConvArgs& p, hipStream_t s) {
     return 0;
 }
 
+// =====================================================================================
+// Host scaffold of the launchers that take a ddnm_conv_desc (conv_igemm_f32, conv_igemm_f16, conv_gather_s16,
+// conv1x1_f16, conv_s16_subpixel).  Shared: the descriptor checks below, the split-K scratch arithmetic and the ConvArgs
+// fill.  Per family: the plan, its split-K constants, the checks only that family makes, the kernel selection.
+// Checks that return the same code commute, so a family may run its own DDNM_E_BADARG tests next to a shared one.
+// =====================================================================================
+// What every family but the sub-pixel form (which has no size test of its own and asks for src1 first) checks first.
+// `no_src1`: the answer to C1 > 0 without src1 -- ddnm_conv2d_f32 has always said DDNM_E_SHAPE there, the others BADARG.
+static inline int conv_check_desc(const ddnm_conv_desc* d, int no_src1 = DDNM_E_BADARG) {
+    if (!d || !d->src0 || !d->weight || !d->out) return DDNM_E_BADARG;
+    if (d->B <= 0 || d->Cout <= 0 || d->Ho <= 0 || d->Wo <= 0) return DDNM_E_BADARG;
+    if (!conv_sizes_addressable(d)) return DDNM_E_SHAPE;
+    if (d->C1 > 0 && !d->src1) return no_src1;
+    return 0;
+}
+
+// GroupNorm prologue and nearest x2 reads (the 1x1 and sub-pixel plans refuse or fix these fields themselves)
+static inline int conv_check_gn_ups(const ddnm_conv_desc* d) {
+    if (d->gn_scale && !d->gn_shift) return DDNM_E_BADARG;
+    if (d->ups && ((d->Hin | d->Win) & 1)) return DDNM_E_SHAPE;
+    if (d->res_ups && ((d->Ho | d->Wo) & 1)) return DDNM_E_SHAPE;
+    return 0;
+}
+
+// fp32 scratch of a launch that splits K `ksplit` ways: one [B*Ho*Wo][Cout] slab per slice, none when unsplit
+static inline int64_t conv_slab_floats(const ddnm_conv_desc* d, int ksplit) {
+    return ksplit > 1 ? (int64_t)ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
+}
+
+// The ksplit to run, given the plan's: without enough scratch the launch runs unsplit -- unless it is to emit
+// statistics, whose buffer the caller sized for the split plan (DDNM_E_BADARG).
+static inline int conv_run_ksplit(const ddnm_conv_desc* d, int ksplit) {
+    if (ksplit <= 1 || (d->workspace && d->workspace_floats >= conv_slab_floats(d, ksplit))) return ksplit;
+    return d->stats_out ? DDNM_E_BADARG : 1;
+}
+
+// statistics tiles per image: split launches emit them from the reduction pass, the others one per M tile of BM pixels
+static inline int conv_stats_tiles(const ddnm_conv_desc* d, int ksplit, int BM) {
+    return ksplit > 1 ? splitk_stats_tiles(d) : d->Ho * d->Wo / BM;
+}
+
+// The one ConvArgs fill.  `d` is the descriptor the kernel sees (conv1x1_f16 passes its folded copy), BM the output
+// pixels per M tile, n_tiles the tiles along Cout.
+static inline ConvArgs conv_args(const ddnm_conv_desc& d, int BM, int n_tiles, int TW, int TW_log2, int tiles_x, int ntaps,
+                                 int ksplit) {
+    ConvArgs p;
+    p.d = d;
+    p.Cin = d.C0 + d.C1;
+    p.ntaps = ntaps;
+    p.Hs = d.ups ? d.Hin / 2 : d.Hin;
+    p.Ws = d.ups ? d.Win / 2 : d.Win;
+    p.m_tiles = d.B * (d.Ho * d.Wo / BM);
+    p.n_tiles = n_tiles;
+    p.TW = TW;
+    p.TW_log2 = TW_log2;
+    p.tiles_x = tiles_x;
+    p.ksplit = ksplit;
+    p.ws = d.workspace;
+    return p;
+}

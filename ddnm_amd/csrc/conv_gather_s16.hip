@@ -216,11 +216,7 @@ static bool plan_gs(const ddnm_conv_desc* d, PlanGS* pl) {
     if ((d->ksize != 1 && d->ksize != 3) || (d->stride != 1 && d->stride != 2)) return false;
     if (d->C0 <= 0 || d->C0 % GS_KC || d->C1 % GS_KC || d->out_nchw || d->src_f16 || d->skip0) return false;
     if (d->Cout % 64 || HWo % 64) return false;
-    {   // the loader addresses both sources with 32-bit buffer offsets and an out-of-range sentinel for padding
-        const int64_t px = (int64_t)d->B * (d->ups ? d->Hin / 2 : d->Hin) * (d->ups ? d->Win / 2 : d->Win);
-        const int64_t cmax = d->C0 > d->C1 ? d->C0 : d->C1;
-        if (px * cmax * 4 >= (int64_t)1 << 31) return false;
-    }
+    if (!conv_operand_offsets_fit(d)) return false;      // (src_f16 was refused above: 4-byte elements)
     const int nchunks = Cin / GS_KC;
     int tile = 2;
     if (HWo % 128 == 0 && d->Cout % 128 == 0) {
@@ -249,47 +245,25 @@ extern "C" int ddnm_conv_gather_s16_supported(const ddnm_conv_desc* d) {
 extern "C" int64_t ddnm_conv_gather_s16_workspace_floats(const ddnm_conv_desc* d) {
     PlanGS pl;
     if (!d || !plan_gs(d, &pl)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
+    return conv_slab_floats(d, pl.ksplit);
 }
 
 extern "C" int ddnm_conv_gather_s16_stats_tiles(const ddnm_conv_desc* d) {
     PlanGS pl;
     if (!d || !plan_gs(d, &pl)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? splitk_stats_tiles(d) : d->Ho * d->Wo / pl.BM;
+    return conv_stats_tiles(d, pl.ksplit, pl.BM);
 }
 
 extern "C" int ddnm_conv_gather_s16_f32(const ddnm_conv_desc* d, void* stream) {
-    if (!d || !d->src0 || !d->weight || !d->out) return DDNM_E_BADARG;
-    if (d->B <= 0 || d->Cout <= 0 || d->Ho <= 0 || d->Wo <= 0) return DDNM_E_BADARG;
-    if (!conv_sizes_addressable(d)) return DDNM_E_SHAPE;
-    if (d->C1 > 0 && !d->src1) return DDNM_E_BADARG;
-    if (d->gn_scale && !d->gn_shift) return DDNM_E_BADARG;
+    if (int e = conv_check_desc(d)) return e;
     if (!(d->acc_scale > 0.f)) return DDNM_E_BADARG;
     if (!d->gn_scale && !d->amax_in) return DDNM_E_BADARG;      // a raw operand needs the operand bound (fp16 range)
-    if (d->ups && ((d->Hin | d->Win) & 1)) return DDNM_E_SHAPE;
-    if (d->res_ups && ((d->Ho | d->Wo) & 1)) return DDNM_E_SHAPE;
+    if (int e = conv_check_gn_ups(d)) return e;
     PlanGS pl;
     if (!plan_gs(d, &pl)) return DDNM_E_SHAPE;
-    if (pl.ksplit > 1) {
-        const int64_t need = (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout;
-        if (!d->workspace || d->workspace_floats < need) {
-            if (d->stats_out) return DDNM_E_BADARG;       // the caller sized stats_out for the split plan
-            pl.ksplit = 1;
-        }
-    }
-    ConvArgs p;
-    p.d = *d;
-    p.Cin = d->C0 + d->C1;
-    p.ntaps = d->ksize * d->ksize;
-    p.Hs = d->ups ? d->Hin / 2 : d->Hin;
-    p.Ws = d->ups ? d->Win / 2 : d->Win;
-    p.m_tiles = d->B * (d->Ho * d->Wo / pl.BM);
-    p.n_tiles = d->Cout / pl.BN;
-    p.TW = 32;
-    p.TW_log2 = 5;
-    p.tiles_x = 0;                 // flat strips of BM consecutive pixels of one image
-    p.ksplit = pl.ksplit;
-    p.ws = d->workspace;
+    if ((pl.ksplit = conv_run_ksplit(d, pl.ksplit)) < 0) return pl.ksplit;
+    // tiles_x = 0: flat strips of BM consecutive pixels of one image
+    const ConvArgs p = conv_args(*d, pl.BM, d->Cout / pl.BN, 32, 5, 0, d->ksize * d->ksize, pl.ksplit);
     const dim3 grid(p.m_tiles * p.n_tiles, pl.ksplit);
     hipStream_t s = (hipStream_t)stream;
     if (pl.tile == 1) { DDNM_LAUNCH((conv_gather_s16_kernel<2, 2, 2, 2>), grid, dim3(256), 0, s, p); }

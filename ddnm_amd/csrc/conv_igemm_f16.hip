@@ -425,11 +425,7 @@ static bool plan_f16(const ddnm_conv_desc* d, PlanF16* pl, int kch = KC16) {
     const int Cin = d->C0 + d->C1;
     if (d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->Ho != d->Hin || d->Wo != d->Win) return false;
     if (Cin % kch || d->C0 % kch || d->Cout % 128 || d->out_nchw) return false;
-    {   // the loader addresses both sources with 32-bit buffer offsets and an out-of-range sentinel for padding
-        const int64_t px = (int64_t)d->B * (d->ups ? d->Hin / 2 : d->Hin) * (d->ups ? d->Win / 2 : d->Win);
-        const int64_t cmax = d->C0 > d->C1 ? d->C0 : d->C1;
-        if (px * cmax * (d->src_f16 ? 2 : 4) >= (int64_t)1 << 31) return false;
-    }
+    if (!conv_operand_offsets_fit(d)) return false;
     pl->BM = F16_BM;
     if (HWo % pl->BM) return false;
     int tw = 32;
@@ -458,54 +454,32 @@ extern "C" int ddnm_conv3x3_f16_supported(const ddnm_conv_desc* d) {
 extern "C" int64_t ddnm_conv3x3_f16_workspace_floats(const ddnm_conv_desc* d) {
     PlanF16 pl;
     if (!d || !plan_f16(d, &pl)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
+    return conv_slab_floats(d, pl.ksplit);
 }
 
 extern "C" int ddnm_conv3x3_f16_stats_tiles(const ddnm_conv_desc* d) {
     PlanF16 pl;
     if (!d || !plan_f16(d, &pl)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? splitk_stats_tiles(d) : d->Ho * d->Wo / pl.BM;
+    return conv_stats_tiles(d, pl.ksplit, pl.BM);
 }
 
 static int run_f16(const ddnm_conv_desc* d, void* stream, bool split) {
     const int kch = split ? KC16 / 2 : KC16;
-    if (!d || !d->src0 || !d->weight || !d->out) return DDNM_E_BADARG;
+    if (!d) return DDNM_E_BADARG;
     if (split && (d->src_f16 || !(d->acc_scale > 0.f))) return DDNM_E_BADARG;
     // raw operands (no GroupNorm in front of the main operand, or a fused shortcut) need the operand bound: fp16 range
     if (split && !d->amax_in && (!d->gn_scale || d->skip0)) return DDNM_E_BADARG;
-    if (d->B <= 0 || d->Cout <= 0 || d->Ho <= 0 || d->Wo <= 0) return DDNM_E_BADARG;
-    if (!conv_sizes_addressable(d)) return DDNM_E_SHAPE;
-    if (d->C1 > 0 && !d->src1) return DDNM_E_BADARG;
-    if (d->gn_scale && !d->gn_shift) return DDNM_E_BADARG;
+    if (int e = conv_check_desc(d)) return e;
     if (d->src_f16 && d->gn_scale) return DDNM_E_BADARG;
-    if (d->ups && ((d->Hin | d->Win) & 1)) return DDNM_E_SHAPE;
-    if (d->res_ups && ((d->Ho | d->Wo) & 1)) return DDNM_E_SHAPE;
+    if (int e = conv_check_gn_ups(d)) return e;
     PlanF16 pl;
     if (!plan_f16(d, &pl, kch)) return DDNM_E_SHAPE;
     if (d->skip0) {
         if (d->ups || !d->skip_weight || d->SC0 <= 0 || d->SC0 % kch || d->SC1 % kch || (d->SC1 > 0 && !d->skip1))
             return DDNM_E_SHAPE;
     }
-    if (pl.ksplit > 1) {
-        const int64_t need = (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout;
-        if (!d->workspace || d->workspace_floats < need) {
-            if (d->stats_out) return DDNM_E_BADARG;
-            pl.ksplit = 1;
-        }
-    }
-    ConvArgs p;
-    p.d = *d;
-    p.Cin = d->C0 + d->C1;
-    p.ntaps = 9;
-    p.Hs = d->ups ? d->Hin / 2 : d->Hin;
-    p.Ws = d->ups ? d->Win / 2 : d->Win;
-    p.m_tiles = d->B * (d->Ho * d->Wo / pl.BM);
-    p.n_tiles = d->Cout / 128;
-    p.TW = pl.TW;
-    p.TW_log2 = pl.TW_log2;
-    p.tiles_x = pl.tiles_x;
-    p.ksplit = pl.ksplit;
-    p.ws = d->workspace;
+    if ((pl.ksplit = conv_run_ksplit(d, pl.ksplit)) < 0) return pl.ksplit;
+    const ConvArgs p = conv_args(*d, pl.BM, d->Cout / 128, pl.TW, pl.TW_log2, pl.tiles_x, 9, pl.ksplit);
     hipStream_t s = (hipStream_t)stream;
     // launches of >= 2 tiles per CU: the persistent form (conv_s16_persist.hip; bit-identical results), unless the caller
     // asks for the one-tile kernel (ddnm_conv_desc::flags & DDNM_CONV_ONE_TILE: A/B timing and the bit-identity tests)
@@ -536,14 +510,7 @@ extern "C" float ddnm_conv3x3_s16_act_scale(void) { return DDNM_S16_ASCALE; }
 extern "C" int ddnm_conv3x3_s16_persistent(const ddnm_conv_desc* d) {
     PlanF16 pl;
     if (!d || (d->flags & DDNM_CONV_UPS_SUBPIXEL) || d->src_f16 || (d->flags & DDNM_CONV_ONE_TILE) || !plan_f16(d, &pl, KC16 / 2) || pl.ksplit != 1) return 0;
-    ConvArgs p;
-    p.d = *d;
-    p.Cin = d->C0 + d->C1;
-    p.m_tiles = d->B * (d->Ho * d->Wo / pl.BM);
-    p.n_tiles = d->Cout / 128;
-    p.TW = pl.TW;
-    p.ksplit = 1;
-    return conv3x3_s16_persist_eligible(p) ? 1 : 0;
+    return conv3x3_s16_persist_eligible(conv_args(*d, pl.BM, d->Cout / 128, pl.TW, pl.TW_log2, pl.tiles_x, 9, 1)) ? 1 : 0;
 }
 
 extern "C" int ddnm_conv3x3_s16_supported(const ddnm_conv_desc* d) {
@@ -555,12 +522,12 @@ extern "C" int64_t ddnm_conv3x3_s16_workspace_floats(const ddnm_conv_desc* d) {
     PlanF16 pl;
     if (d && (d->flags & DDNM_CONV_UPS_SUBPIXEL)) return conv3x3_s16_ups_subpixel_ok(d) ? 0 : DDNM_E_SHAPE;      // never split-K
     if (!d || !plan_f16(d, &pl, KC16 / 2)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
+    return conv_slab_floats(d, pl.ksplit);
 }
 
 extern "C" int ddnm_conv3x3_s16_stats_tiles(const ddnm_conv_desc* d) {
     PlanF16 pl;
     if (d && (d->flags & DDNM_CONV_UPS_SUBPIXEL)) return conv3x3_s16_ups_subpixel_ok(d) ? d->Ho * d->Wo / 256 : DDNM_E_SHAPE;
     if (!d || !plan_f16(d, &pl, KC16 / 2)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? splitk_stats_tiles(d) : d->Ho * d->Wo / pl.BM;
+    return conv_stats_tiles(d, pl.ksplit, pl.BM);
 }

@@ -429,14 +429,13 @@ extern "C" int ddnm_conv2d_f32_stats_tiles(const ddnm_conv_desc* d) {
     ConvPlan pl;
     if (!d || !make_plan(d, &pl)) return DDNM_E_SHAPE;
     if (d->out_nchw) return 0;                          // NCHW launches do not emit statistics
-    if (pl.ksplit > 1) return splitk_stats_tiles(d);    // ... split-K launches emit them from the reduction pass
-    return d->Ho * d->Wo / pl.BM;
+    return conv_stats_tiles(d, pl.ksplit, pl.BM);
 }
 
 extern "C" int64_t ddnm_conv2d_f32_workspace_floats(const ddnm_conv_desc* d) {
     ConvPlan pl;
     if (!d || !make_plan(d, &pl)) return DDNM_E_SHAPE;
-    return pl.ksplit > 1 ? (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout : 0;
+    return conv_slab_floats(d, pl.ksplit);
 }
 
 template <int WM, int WN, int MT, int NT>
@@ -448,15 +447,11 @@ static void launch_conv(bool halo, dim3 grid, hipStream_t s, const ConvArgs& p) 
 }
 
 extern "C" int ddnm_conv2d_f32(const ddnm_conv_desc* d, void* stream) {
-    if (!d || !d->src0 || !d->weight || !d->out) return DDNM_E_BADARG;
-    if (d->B <= 0 || d->Cout <= 0 || d->Ho <= 0 || d->Wo <= 0) return DDNM_E_BADARG;
-    if (!conv_sizes_addressable(d)) return DDNM_E_SHAPE;
-    if (d->C0 <= 0 || d->C0 % KC || d->C1 % KC || (d->C1 > 0 && !d->src1)) return DDNM_E_SHAPE;
+    if (int e = conv_check_desc(d, DDNM_E_SHAPE)) return e;      // this family files a missing src1 under its channel rules
+    if (d->C0 <= 0 || d->C0 % KC || d->C1 % KC) return DDNM_E_SHAPE;
     if ((d->ksize != 1 && d->ksize != 3) || (d->stride != 1 && d->stride != 2)) return DDNM_E_SHAPE;
-    if (d->gn_scale && !d->gn_shift) return DDNM_E_BADARG;
-    if (d->ups && ((d->Hin | d->Win) & 1)) return DDNM_E_SHAPE;
+    if (int e = conv_check_gn_ups(d)) return e;
     if (d->out_nchw && d->res) return DDNM_E_SHAPE;
-    if (d->res_ups && ((d->Ho | d->Wo) & 1)) return DDNM_E_SHAPE;
     ConvPlan pl;
     if (!make_plan(d, &pl)) return DDNM_E_SHAPE;
     if (d->skip0) {
@@ -464,27 +459,9 @@ extern "C" int ddnm_conv2d_f32(const ddnm_conv_desc* d, void* stream) {
             (d->SC1 > 0 && !d->skip1))
             return DDNM_E_SHAPE;
     }
-    if (pl.ksplit > 1) {
-        const int64_t need = (int64_t)pl.ksplit * d->B * d->Ho * d->Wo * d->Cout;
-        if (!d->workspace || d->workspace_floats < need) {
-            if (d->stats_out) return DDNM_E_BADARG;       // the caller sized stats_out for the split plan
-            pl.ksplit = 1;                                // no scratch: run unsplit
-        }
-    }
+    if ((pl.ksplit = conv_run_ksplit(d, pl.ksplit)) < 0) return pl.ksplit;
     if (d->stats_out && d->out_nchw) return DDNM_E_SHAPE;                     // see ddnm_conv2d_f32_stats_tiles
-    ConvArgs p;
-    p.d = *d;
-    p.Cin = d->C0 + d->C1;
-    p.ntaps = d->ksize * d->ksize;
-    p.Hs = d->ups ? d->Hin / 2 : d->Hin;
-    p.Ws = d->ups ? d->Win / 2 : d->Win;
-    p.m_tiles = d->B * (d->Ho * d->Wo / pl.BM);
-    p.n_tiles = (d->Cout + pl.BN - 1) / pl.BN;
-    p.TW = pl.TW;
-    p.TW_log2 = pl.TW_log2;
-    p.tiles_x = pl.tiles_x;
-    p.ksplit = pl.ksplit;
-    p.ws = d->workspace;
+    const ConvArgs p = conv_args(*d, pl.BM, (d->Cout + pl.BN - 1) / pl.BN, pl.TW, pl.TW_log2, pl.tiles_x, d->ksize * d->ksize, pl.ksplit);
     dim3 grid(p.m_tiles * p.n_tiles, pl.ksplit);
     hipStream_t s = (hipStream_t)stream;
     (void)hipGetLastError();      // drop stale errors of unrelated runtime calls

@@ -444,19 +444,8 @@ int conv3x3_s16_ups_subpixel_run(const ddnm_conv_desc* d, hipStream_t s) {
     if (!d || !d->src0 || !d->weight || !d->out || !d->amax_in || !(d->acc_scale > 0.f)) return DDNM_E_BADARG;
     if (d->C1 > 0 && !d->src1) return DDNM_E_BADARG;
     if (!conv3x3_s16_ups_subpixel_ok(d)) return DDNM_E_SHAPE;
-    ConvArgs p;
-    p.d = *d;
-    p.Cin = d->C0 + d->C1;
-    p.ntaps = Q_STEPS;
-    p.Hs = d->Hin / 2;
-    p.Ws = d->Win / 2;
-    p.m_tiles = d->B * (p.Hs * p.Ws / 256);
-    p.n_tiles = d->Cout / 32;                             // (64-channel block, py): 128 rows each
-    p.TW = 32;
-    p.TW_log2 = 5;
-    p.tiles_x = p.Ws / 32;
-    p.ksplit = 1;
-    p.ws = nullptr;
+    // M tiles of 256 source pixels = 1024 output pixels; n_tiles counts (64-channel block, py) pairs of 128 rows each
+    const ConvArgs p = conv_args(*d, 1024, d->Cout / 32, 32, 5, d->Win / 2 / 32, Q_STEPS, 1);
     const int total = p.m_tiles * p.n_tiles;
     const int cus = conv_persist_grid_cus();
     DDNM_LAUNCH(conv2x2x4_s16_subpixel_kernel, dim3(total < cus ? total : cus), dim3(Q_NTHREADS), 0, s, p, total);

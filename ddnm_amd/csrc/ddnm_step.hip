@@ -107,15 +107,25 @@ __global__ __launch_bounds__(256) void step_combine_kernel(const float* __restri
     }
 }
 
+// Host side of a step kernel that exists for both noise sources: the extern "C" pair (here and under "keyed entry points")
+// checks its pointers and its source, builds the source and calls the one launcher below its kernel, which checks the
+// sizes (DDNM_E_BADARG before DDNM_E_SHAPE, as everywhere), sizes the grid and launches kernel<Src>.
+template <class Src>
+static int launch_step_combine(const float* x0, const float* proj, const float* apy, Src src, const float* et, int64_t et_bstride,
+                               float* xt_next, int32_t B, int64_t chw, const ddnm_step_scalars* s, void* stream) {
+    if (B <= 0 || chw <= 0) return DDNM_E_BADARG;
+    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)B * chw / 4;
+    DDNM_LAUNCH(step_combine_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x0, proj, apy, src, et, et_bstride,
+                xt_next, chw / 4, total4, *s);
+    return 0;
+}
+
 extern "C" int ddnm_step_combine_f32(const float* x0, const float* proj, const float* apy, const float* noise,
                                      const float* et, int64_t et_bstride, float* xt_next, int32_t B, int64_t chw,
                                      const ddnm_step_scalars* s, void* stream) {
-    if (!x0 || !proj || !et || !xt_next || !s || B <= 0 || chw <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
-    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(step_combine_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x0, proj, apy, noise_src(noise, s, chw),
-                       et, et_bstride, xt_next, chw / 4, total4, *s);
-    return 0;
+    if (!x0 || !proj || !et || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_combine(x0, proj, apy, noise_src(noise, s, chw), et, et_bstride, xt_next, B, chw, s, stream);
 }
 
 // ---------------------------------------------------------------- fused: SR by average pooling, r = 4
@@ -156,16 +166,22 @@ __global__ __launch_bounds__(256) void step_sr4_kernel(const float* __restrict__
     }
 }
 
+template <class Src>
+static int launch_step_sr4(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0, float* xt_next,
+                           int32_t B, int32_t H, int32_t W, int32_t r, const ddnm_step_scalars* s, void* stream) {
+    if (B <= 0) return DDNM_E_BADARG;
+    if (r != 4 || (H & 3) || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total = (int64_t)B * 3 * (H / 4) * (W / 4);
+    DDNM_LAUNCH(step_sr4_kernel<Src>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, x0, xt_next, H,
+                W, total, *s);
+    return 0;
+}
+
 extern "C" int ddnm_step_sr_avgpool_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
                                         const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W,
                                         int32_t r, const ddnm_step_scalars* s, void* stream) {
-    if (!xt || !et || !y || !xt_next || !s || B <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
-    if (r != 4 || (H & 3) || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total = (int64_t)B * 3 * (H / 4) * (W / 4);
-    DDNM_LAUNCH(step_sr4_kernel<NoiseSrc>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                noise_src(noise, s, (int64_t)3 * H * W),
-                       y, x0, xt_next, H, W, total, *s);
-    return 0;
+    if (!xt || !et || !y || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_sr4(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, x0, xt_next, B, H, W, r, s, stream);
 }
 
 // ---------------------------------------------------------------- fused: colorization
@@ -208,15 +224,22 @@ __global__ __launch_bounds__(256) void step_color_kernel(const float* __restrict
     }
 }
 
+template <class Src>
+static int launch_step_color(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0, float* xt_next,
+                             int32_t B, int32_t HW, const float* w3_host, const ddnm_step_scalars* s, void* stream) {
+    if (B <= 0 || HW <= 0) return DDNM_E_BADARG;
+    if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    const int64_t total4 = (int64_t)B * HW / 4;
+    DDNM_LAUNCH(step_color_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, x0, xt_next,
+                (int64_t)HW / 4, total4, *s, color_weights(w3_host));
+    return 0;
+}
+
 extern "C" int ddnm_step_color_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
                                    const float* y, float* x0, float* xt_next, int32_t B, int32_t HW,
                                    const float* w3_host, const ddnm_step_scalars* s, void* stream) {
-    if (!xt || !et || !y || !xt_next || !s || B <= 0 || HW <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
-    if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_color_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                       noise_src(noise, s, (int64_t)3 * HW), y, x0, xt_next, (int64_t)HW / 4, total4, *s, color_weights(w3_host));
-    return 0;
+    if (!xt || !et || !y || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_color(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * HW), y, x0, xt_next, B, HW, w3_host, s, stream);
 }
 
 // ---------------------------------------------------------------- fused: inpainting (mask as rank table)
@@ -251,16 +274,24 @@ __global__ __launch_bounds__(256) void step_inpaint_kernel(const float* __restri
     }
 }
 
+// one launcher for the shared-mask and the per-image (*_pi_*) entry points; the latter check y_stride / n_kept_max first
+template <class Src>
+static int launch_step_inpaint(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, int64_t y_bstride,
+                               const int32_t* rank, int64_t rank_bstride, float* x0, float* xt_next, int32_t B, int32_t HW,
+                               const ddnm_step_scalars* s, void* stream) {
+    const int64_t total4 = (int64_t)B * HW / 4;
+    DDNM_LAUNCH(step_inpaint_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, y_bstride,
+                rank, rank_bstride, x0, xt_next, (int64_t)HW / 4, total4, *s);
+    return 0;
+}
+
 extern "C" int ddnm_step_inpaint_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
                                      const float* y, const int32_t* rank, int32_t n_kept, float* x0, float* xt_next,
                                      int32_t B, int32_t HW, const ddnm_step_scalars* s, void* stream) {
     if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_inpaint_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                       noise_src(noise, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0, xt_next, (int64_t)HW / 4,
-                       total4, *s);
-    return 0;
+    return launch_step_inpaint(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0,
+                               xt_next, B, HW, s, stream);
 }
 
 // one mask per image: rank [B][HW], y [B][y_stride] (row b: 3 * n_kept[b] entries, then padding that is never read)
@@ -276,11 +307,8 @@ extern "C" int ddnm_step_inpaint_pi_f32(const float* xt, const float* et, int64_
     if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
     if (et_bstride & 3) return DDNM_E_SHAPE;
     if (int e = inpaint_pi_args(n_kept_max, y_stride, HW)) return e;
-    const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_inpaint_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                noise_src(noise, s, (int64_t)3 * HW), y, y_stride, rank, (int64_t)HW, x0, xt_next, (int64_t)HW / 4, total4,
-                *s);
-    return 0;
+    return launch_step_inpaint(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * HW), y, y_stride, rank, (int64_t)HW, x0, xt_next,
+                               B, HW, s, stream);
 }
 
 extern "C" int ddnm_step_inpaint_pi_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
@@ -290,11 +318,8 @@ extern "C" int ddnm_step_inpaint_pi_keyed_f32(const float* xt, const float* et, 
     if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
     if (et_bstride & 3) return DDNM_E_SHAPE;
     if (int e = inpaint_pi_args(n_kept_max, y_stride, HW)) return e;
-    const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_inpaint_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                keyed_src(keys, s, (int64_t)3 * HW), y, y_stride, rank, (int64_t)HW, x0, xt_next, (int64_t)HW / 4, total4,
-                *s);
-    return 0;
+    return launch_step_inpaint(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * HW), y, y_stride, rank, (int64_t)HW, x0, xt_next,
+                               B, HW, s, stream);
 }
 
 // ---------------------------------------------------------------- fused: denoising (A = I)
@@ -315,49 +340,44 @@ __global__ __launch_bounds__(256) void step_denoise_kernel(const float* __restri
     }
 }
 
-extern "C" int ddnm_step_denoise_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
-                                     const float* y, float* x0, float* xt_next, int32_t B, int64_t chw,
-                                     const ddnm_step_scalars* s, void* stream) {
-    if (!xt || !et || !y || !xt_next || !s || B <= 0 || chw <= 0 || !noise_ok(noise, s)) return DDNM_E_BADARG;
+template <class Src>
+static int launch_step_denoise(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0, float* xt_next,
+                               int32_t B, int64_t chw, const ddnm_step_scalars* s, void* stream) {
+    if (B <= 0 || chw <= 0) return DDNM_E_BADARG;
     if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     const int64_t total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(step_denoise_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                       noise_src(noise, s, chw), y, x0, xt_next, chw / 4, total4, *s);
+    DDNM_LAUNCH(step_denoise_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, x0, xt_next,
+                chw / 4, total4, *s);
     return 0;
 }
 
-// ---------------------------------------------------------------- keyed entry points: same kernels, per-image keys
+extern "C" int ddnm_step_denoise_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                     const float* y, float* x0, float* xt_next, int32_t B, int64_t chw,
+                                     const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_denoise(xt, et, et_bstride, noise_src(noise, s, chw), y, x0, xt_next, B, chw, s, stream);
+}
+
+// ---------------------------------------------------------------- keyed entry points: same launchers, per-image keys
 extern "C" int ddnm_step_combine_keyed_f32(const float* x0, const float* proj, const float* apy, const uint32_t* keys,
                                            const float* et, int64_t et_bstride, float* xt_next, int32_t B, int64_t chw,
                                            const ddnm_step_scalars* s, void* stream) {
-    if (!x0 || !proj || !et || !xt_next || !s || B <= 0 || chw <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
-    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(step_combine_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x0, proj, apy,
-                keyed_src(keys, s, chw), et, et_bstride, xt_next, chw / 4, total4, *s);
-    return 0;
+    if (!x0 || !proj || !et || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_combine(x0, proj, apy, keyed_src(keys, s, chw), et, et_bstride, xt_next, B, chw, s, stream);
 }
 
 extern "C" int ddnm_step_sr_avgpool_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
                                               const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W,
                                               int32_t r, const ddnm_step_scalars* s, void* stream) {
-    if (!xt || !et || !y || !xt_next || !s || B <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
-    if (r != 4 || (H & 3) || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total = (int64_t)B * 3 * (H / 4) * (W / 4);
-    DDNM_LAUNCH(step_sr4_kernel<KeyedNoiseSrc>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                keyed_src(keys, s, (int64_t)3 * H * W), y, x0, xt_next, H, W, total, *s);
-    return 0;
+    if (!xt || !et || !y || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_sr4(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, x0, xt_next, B, H, W, r, s, stream);
 }
 
 extern "C" int ddnm_step_color_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
                                          const float* y, float* x0, float* xt_next, int32_t B, int32_t HW,
                                          const float* w3_host, const ddnm_step_scalars* s, void* stream) {
-    if (!xt || !et || !y || !xt_next || !s || B <= 0 || HW <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
-    if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_color_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                keyed_src(keys, s, (int64_t)3 * HW), y, x0, xt_next, (int64_t)HW / 4, total4, *s, color_weights(w3_host));
-    return 0;
+    if (!xt || !et || !y || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_color(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * HW), y, x0, xt_next, B, HW, w3_host, s, stream);
 }
 
 extern "C" int ddnm_step_inpaint_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
@@ -365,22 +385,15 @@ extern "C" int ddnm_step_inpaint_keyed_f32(const float* xt, const float* et, int
                                            int32_t B, int32_t HW, const ddnm_step_scalars* s, void* stream) {
     if (!xt || !et || !y || !rank || !xt_next || !s || B <= 0 || HW <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * HW / 4;
-    DDNM_LAUNCH(step_inpaint_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                keyed_src(keys, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0, xt_next, (int64_t)HW / 4,
-                total4, *s);
-    return 0;
+    return launch_step_inpaint(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0,
+                               xt_next, B, HW, s, stream);
 }
 
 extern "C" int ddnm_step_denoise_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
                                            const float* y, float* x0, float* xt_next, int32_t B, int64_t chw,
                                            const ddnm_step_scalars* s, void* stream) {
-    if (!xt || !et || !y || !xt_next || !s || B <= 0 || chw <= 0 || !keys_ok(keys)) return DDNM_E_BADARG;
-    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
-    const int64_t total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(step_denoise_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                keyed_src(keys, s, chw), y, x0, xt_next, chw / 4, total4, *s);
-    return 0;
+    if (!xt || !et || !y || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_denoise(xt, et, et_bstride, keyed_src(keys, s, chw), y, x0, xt_next, B, chw, s, stream);
 }
 
 // ---------------------------------------------------------------- stand-alone Philox draw
@@ -925,18 +938,26 @@ static inline int plus_spectral_args(const float* xt_hat, const float* et_hat, c
     return 0;
 }
 
+template <class Src>      // after plus_spectral_args and the source check of the entry point
+static int launch_plus_spectral(const float* xt_hat, const float* et_hat, const float* y_hat, const float* gains, int64_t gains_cstride,
+                                Src src, float* out_hat, int32_t B, int64_t chw, int64_t plane, float sigma_y, float sigma_t, float eta,
+                                const ddnm_step_scalars* s, void* stream) {
+    const int64_t total4 = (int64_t)B * chw / 4;
+    const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
+    DDNM_LAUNCH(step_plus_spectral_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt_hat, et_hat, y_hat, gains,
+                gains_cstride, src, out_hat, plane / 4, chw / 4, total4, *s, sigma_y, sigma_t, eta, eta_c);
+    return 0;
+}
+
 extern "C" int ddnm_step_plus_spectral_f32(const float* xt_hat, const float* et_hat, const float* y_hat,
                                            const float* gains, int64_t gains_cstride, const float* noise, float* out_hat,
                                            int32_t B, int32_t C, int64_t plane, float sigma_y, float sigma_t, float eta,
                                            const ddnm_step_scalars* s, void* stream) {
     if (int e = plus_spectral_args(xt_hat, et_hat, y_hat, gains, gains_cstride, out_hat, B, C, plane, s)) return e;
     if (!noise_ok(noise, s)) return DDNM_E_BADARG;
-    const int64_t chw = (int64_t)C * plane, total4 = (int64_t)B * chw / 4;
-    const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
-    DDNM_LAUNCH(step_plus_spectral_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt_hat, et_hat,
-                y_hat, gains, gains_cstride, noise_src(noise, s, chw), out_hat, plane / 4, chw / 4, total4, *s, sigma_y,
-                sigma_t, eta, eta_c);
-    return 0;
+    const int64_t chw = (int64_t)C * plane;
+    return launch_plus_spectral(xt_hat, et_hat, y_hat, gains, gains_cstride, noise_src(noise, s, chw), out_hat, B, chw, plane, sigma_y,
+                                sigma_t, eta, s, stream);
 }
 
 extern "C" int ddnm_step_plus_spectral_keyed_f32(const float* xt_hat, const float* et_hat, const float* y_hat,
@@ -945,12 +966,9 @@ extern "C" int ddnm_step_plus_spectral_keyed_f32(const float* xt_hat, const floa
                                                  float sigma_t, float eta, const ddnm_step_scalars* s, void* stream) {
     if (int e = plus_spectral_args(xt_hat, et_hat, y_hat, gains, gains_cstride, out_hat, B, C, plane, s)) return e;
     if (!keys_ok(keys)) return DDNM_E_BADARG;
-    const int64_t chw = (int64_t)C * plane, total4 = (int64_t)B * chw / 4;
-    const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
-    DDNM_LAUNCH(step_plus_spectral_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt_hat,
-                et_hat, y_hat, gains, gains_cstride, keyed_src(keys, s, chw), out_hat, plane / 4, chw / 4, total4, *s,
-                sigma_y, sigma_t, eta, eta_c);
-    return 0;
+    const int64_t chw = (int64_t)C * plane;
+    return launch_plus_spectral(xt_hat, et_hat, y_hat, gains, gains_cstride, keyed_src(keys, s, chw), out_hat, B, chw, plane, sigma_y,
+                                sigma_t, eta, s, stream);
 }
 
 // out[b][i] = a * x[b*x_bstride + i] + b * y[b*chw + i]: eps <- eps[:, :3] - sqrt(1-abar) * grad  (svd_ddnm.py:51-52)
@@ -1057,17 +1075,25 @@ static inline int plus_cs_pre_args(const float* xt, const float* et, int64_t et_
     return 0;
 }
 
+template <class Src>      // after plus_cs_pre_args and the source check of the entry point
+static int launch_plus_cs_pre(const float* xt, const float* et, int64_t et_bstride, Src src, const float* aty, float* x0_out,
+                              float* xt_next, float* w, int32_t B, int32_t C, int32_t D, int32_t ps, int64_t chw, CsPlusCoef k,
+                              const ddnm_step_scalars* s, void* stream) {
+    const int64_t total4 = (int64_t)B * chw / 4;
+    DDNM_LAUNCH(cs_plus_pre_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, aty, x0_out,
+                xt_next, w, C, D, ps, chw / 4, total4, *s, k);
+    return 0;
+}
+
 extern "C" int ddnm_step_plus_cs_pre_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
                                          const float* aty, float* x0_out, float* xt_next, float* w, int32_t B, int32_t C,
                                          int32_t D, int32_t ps, float a_lambda, float d1n, float d2n, float dd1,
                                          float dd2, const ddnm_step_scalars* s, void* stream) {
     if (int e = plus_cs_pre_args(xt, et, et_bstride, aty, x0_out, xt_next, w, B, C, D, ps, s)) return e;
     if (!noise_ok(noise, s)) return DDNM_E_BADARG;
-    const int64_t chw = (int64_t)C * D * D, total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(cs_plus_pre_kernel<NoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride,
-                noise_src(noise, s, chw), aty, x0_out, xt_next, w, C, D, ps, chw / 4, total4, *s,
-                CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2});
-    return 0;
+    const int64_t chw = (int64_t)C * D * D;
+    return launch_plus_cs_pre(xt, et, et_bstride, noise_src(noise, s, chw), aty, x0_out, xt_next, w, B, C, D, ps, chw,
+                              CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2}, s, stream);
 }
 
 extern "C" int ddnm_step_plus_cs_pre_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
@@ -1076,11 +1102,9 @@ extern "C" int ddnm_step_plus_cs_pre_keyed_f32(const float* xt, const float* et,
                                                float dd1, float dd2, const ddnm_step_scalars* s, void* stream) {
     if (int e = plus_cs_pre_args(xt, et, et_bstride, aty, x0_out, xt_next, w, B, C, D, ps, s)) return e;
     if (!keys_ok(keys)) return DDNM_E_BADARG;
-    const int64_t chw = (int64_t)C * D * D, total4 = (int64_t)B * chw / 4;
-    DDNM_LAUNCH(cs_plus_pre_kernel<KeyedNoiseSrc>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et,
-                et_bstride, keyed_src(keys, s, chw), aty, x0_out, xt_next, w, C, D, ps, chw / 4, total4, *s,
-                CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2});
-    return 0;
+    const int64_t chw = (int64_t)C * D * D;
+    return launch_plus_cs_pre(xt, et, et_bstride, keyed_src(keys, s, chw), aty, x0_out, xt_next, w, B, C, D, ps, chw,
+                              CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2}, s, stream);
 }
 
 // xt_next[img] += P[patch index]: the inverse gather of patchify_kernel with an add (2 reads, 1 write per element)

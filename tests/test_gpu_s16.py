@@ -109,9 +109,10 @@ def test_split_kernel_is_at_least_as_close_to_fp64_as_the_fp32_kernel(case):
     assert ((a16.t - a32.t).norm() / a32.t.norm()).item() < 1.5e-6
 
 
-# Launches of >= 2 tiles per CU (>= 512 tiles, no split-K, no fused shortcut) run the PERSISTENT form of the kernel
+# Launches of >= 2 tiles per CU (>= 512 tiles, no split-K) run the PERSISTENT form of the kernel
 # (csrc/conv_s16_persist.hip, round 6): tiles walked by one workgroup per CU, the next tile's halo / weights prefetched in
-# the last chunk, the epilogue's stores and residual loads spread over the neighbouring chunks.
+# the last chunk, the epilogue's stores and residual loads spread over the neighbouring chunks.  A fused 1x1 shortcut
+# (raw shortcut operand with its bound, no residual) runs there too; the cases below carry none.
 # B, C0, C1, Cout, H, ups, gn, res, skip, badd
 PERSIST_CASES = [
     (8, 128, 0, 128, 128, 0, 1, 1, 0, 1),     # 512 tiles (2 per CU): GroupNorm + swish, temb addend, residual, 4 chunks
