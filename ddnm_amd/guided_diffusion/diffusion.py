@@ -27,7 +27,14 @@ Deliberate differences at the boundary (not in the results):
     under `--seed seed + k` (sample_sources) and all K with the one measurement y of the run's own seed: `{i}_{k}.png` for
     every k (the reference hard-wires the 0), `mean/mean_{i}.png` (the posterior mean) and `std/std_{i}.png` (the
     per-pixel standard deviation, ops.sample_stats, csrc/metrics.hip).  The PSNR / SSIM lines stay those of sample 0.
+
+All of these run through ONE path of `Diffusion.svd_based_ddnm_plus`: the plan (`fuse_groups`: which loader batches this
+rank restores, grouped into sampler calls; `restored_images` is the same plan as image indices), `prepare` (a loader batch
+-> a `Part`: y, Apy files, x_T and one noise source per sample), `restore` (a group of parts -> one sampler call, the only
+one) and `finish` (one part's rows -> gather in split mode, PNGs, metric lines, K-sample statistics).  The plain run is
+the case of one part per call and one sample per image.
 """
+import collections
 import os
 import random
 
@@ -39,8 +46,8 @@ from .. import dist as ddist
 from .. import ops
 from ..functions.svd_ddnm import (_AtenNoise, _reverse_loop, _TapeNoise, ddnm_diffusion, ddnm_plus_diffusion,
                                   get_schedule_jump)
-from ..functions.svd_operators import (Colorization, Denoising, Inpainting, InpaintingBank, PerImageInpainting,
-                                      SuperResolution, build_operator, mask_color_sr)
+from ..functions.svd_operators import (Colorization, Denoising, Inpainting, InpaintingBank, SuperResolution,
+                                      build_operator, mask_color_sr)
 from .models import Model
 
 
@@ -422,16 +429,33 @@ def restored_images(n_items, batch_size, rank, world, k, start=0):
     in call order: the whole batches of a fused group (one rank, deal mode) or this rank's slice [lo, hi) of one batch
     (split mode); a call without images (fewer images than ranks) is left out.  With a mask bank of N masks image i is
     restored with mask i % N, whichever call it lands in."""
-    split = world > 1 and batch_size >= world
     calls = []
     for group in fuse_groups(n_items, batch_size, rank, world, k):
         idx = []
         for _, first, b in group:
-            lo, hi = ddist.shard_range(b, rank, world) if split else (0, b)
+            lo, hi = rank_slice(b, batch_size, rank, world)
             idx += range(start + first + lo, start + first + hi)
         if idx:
             calls.append(idx)
     return calls
+
+
+def rank_slice(b, batch_size, rank, world):
+    """[lo, hi) of the `b` images of one loader batch that `rank` restores: its shard in split mode (batch_size >= world
+    > 1), the whole batch otherwise (one rank, or deal mode: fuse_groups lists the batches a rank owns)."""
+    return ddist.shard_range(b, rank, world) if world > 1 and batch_size >= world else (0, b)
+
+
+# What one rank restores of one loader batch (Diffusion.svd_based_ddnm_plus): batch index `bi`, global index `idx0` of the
+# batch's first image, batch size `b`, this rank's images [lo, hi) of it, `x_orig` [b] on the [-1, 1] scale, the
+# measurement rows `y` [hi - lo], `x_T` [NS * (hi - lo)] ordered [sample k][image j], and `noise`: one source per sample
+# (ops.PhiloxNoise with image_base = lo, or a BatchNoise tape under DDNM_NOISE=torch)
+Part = collections.namedtuple("Part", "bi idx0 b lo hi x_orig y x_T noise")
+
+
+def _cat(tensors):
+    """torch.cat along the rows that launches nothing for a single tensor."""
+    return tensors[0] if len(tensors) == 1 else torch.cat(tensors, 0)
 
 
 class Diffusion(object):
@@ -450,19 +474,26 @@ class Diffusion(object):
         self.num_timesteps = self.betas.shape[0]
 
     # ------------------------------------------------------------------ model construction
+    @staticmethod
+    def _load_weights(net, ckpt, random_weights, announce=True):
+        """The checkpoint `ckpt` if it exists, else `random_weights()` under DDNM_RANDOM_WEIGHTS=1, else an error
+        (`announce=False`, the classifier: no line about the random weights, and the shorter error text)."""
+        if os.path.exists(ckpt):
+            net.load_state_dict(torch.load(ckpt, map_location="cpu"))
+        elif os.environ.get("DDNM_RANDOM_WEIGHTS") == "1":
+            if announce:
+                print(f"[ddnm_amd] {ckpt} not found; DDNM_RANDOM_WEIGHTS=1 -> seeded random weights")
+            net.load_state_dict(random_weights())
+        else:
+            place = "no network here: place the checkpoint there, or " if announce else ""
+            raise FileNotFoundError(f"{ckpt} not found ({place}set DDNM_RANDOM_WEIGHTS=1 for seeded random weights)")
+
     def _build_model(self):
         cfg = self.config
         if cfg.model.type == "simple":
             model = Model(cfg, device=self.device)
-            ckpt = simple_checkpoint_path(cfg, self.args.exp)
-            if os.path.exists(ckpt):
-                model.load_state_dict(torch.load(ckpt, map_location="cpu"))
-            elif os.environ.get("DDNM_RANDOM_WEIGHTS") == "1":
-                print(f"[ddnm_amd] {ckpt} not found; DDNM_RANDOM_WEIGHTS=1 -> seeded random weights")
-                model.load_state_dict(model.random_state_dict(self.args.seed))
-            else:
-                raise FileNotFoundError(f"{ckpt} not found (no network here: place the checkpoint there, or set "
-                                        "DDNM_RANDOM_WEIGHTS=1 for seeded random weights)")
+            self._load_weights(model, simple_checkpoint_path(cfg, self.args.exp),
+                               lambda: model.random_state_dict(self.args.seed))
             return model
         if cfg.model.type == "openai":
             from .unet import create_model
@@ -475,14 +506,7 @@ class Diffusion(object):
                     cfg.data.image_size, cfg.data.image_size))
             else:
                 ckpt = os.path.join(self.args.exp, "logs/imagenet/256x256_diffusion_uncond.pt")
-            if os.path.exists(ckpt):
-                model.load_state_dict(torch.load(ckpt, map_location="cpu"))
-            elif os.environ.get("DDNM_RANDOM_WEIGHTS") == "1":
-                print(f"[ddnm_amd] {ckpt} not found; DDNM_RANDOM_WEIGHTS=1 -> seeded random weights")
-                model.load_state_dict(model.random_state_dict(self.args.seed))
-            else:
-                raise FileNotFoundError(f"{ckpt} not found (no network here: place the checkpoint there, or set "
-                                        "DDNM_RANDOM_WEIGHTS=1 for seeded random weights)")
+            self._load_weights(model, ckpt, lambda: model.random_state_dict(self.args.seed))
             if cfg.model.class_cond:
                 # noisy classifier + guidance gradient (diffusion.py:166-191)
                 from .classifier import args_to_dict, classifier_defaults, create_classifier, make_cond_fn
@@ -490,17 +514,15 @@ class Diffusion(object):
                     cfg.data.image_size, cfg.data.image_size))
                 classifier = create_classifier(**args_to_dict(cfg.classifier, classifier_defaults().keys()))
                 classifier.device = self.device
-                if os.path.exists(ckpt):
-                    classifier.load_state_dict(torch.load(ckpt, map_location="cpu"))
-                elif os.environ.get("DDNM_RANDOM_WEIGHTS") == "1":
+
+                def random_classifier():
                     g = torch.Generator().manual_seed(self.args.seed + 1)
-                    sd = {k: (torch.randn(v, generator=g) * (1.0 / max(1, int(np.prod(v[1:])))) ** 0.5 if len(v) > 1
-                              else (1.0 + 0.1 * torch.randn(v, generator=g) if k.endswith("weight") else
-                                    0.05 * torch.randn(v, generator=g)))
-                          for k, v in classifier.state_dict_shapes().items()}
-                    classifier.load_state_dict(sd)
-                else:
-                    raise FileNotFoundError(f"{ckpt} not found (set DDNM_RANDOM_WEIGHTS=1 for seeded random weights)")
+                    return {k: (torch.randn(v, generator=g) * (1.0 / max(1, int(np.prod(v[1:])))) ** 0.5 if len(v) > 1
+                                else (1.0 + 0.1 * torch.randn(v, generator=g) if k.endswith("weight") else
+                                      0.05 * torch.randn(v, generator=g)))
+                            for k, v in classifier.state_dict_shapes().items()}
+
+                self._load_weights(classifier, ckpt, random_classifier, announce=False)
                 if cfg.classifier.classifier_use_fp16:
                     classifier.convert_to_fp16()
                 self._cls_fn = make_cond_fn(classifier, cfg.classifier.classifier_scale)
@@ -580,6 +602,22 @@ class Diffusion(object):
                                worker_init_fn=seed_worker, generator=g)
 
     # ------------------------------------------------------------------ SVD path (diffusion.py:419-610)
+    def _write_apy(self, A_funcs, y, x_orig, idx0):
+        """`Apy/Apy_{i}.png` (A^+ y, or what the reference shows in its place for the task) and `Apy/orig_{i}.png` of one
+        loader batch whose first image has the global index `idx0`."""
+        args, (b, C, S, _) = self.args, x_orig.shape
+        Apy = A_funcs.A_pinv(y).view(b, C, S, S)
+        if args.deg[:6] == "deblur":
+            Apy = y.view(b, C, S, S)
+        elif args.deg == "colorization":
+            Apy = y.view(b, 1, S, S).repeat(1, 3, 1, 1)
+        elif args.deg == "inpainting":
+            Apy = Apy + A_funcs.A_pinv(A_funcs.A(torch.ones_like(Apy))).reshape(*Apy.shape) - 1
+        for i in range(b):
+            save_image(ops.finalize_psnr(Apy[i:i + 1].contiguous())[0][0],
+                       os.path.join(args.image_folder, f"Apy/Apy_{idx0 + i}.png"))
+            save_image(ops.finalize_psnr(x_orig[i:i + 1])[0][0], os.path.join(args.image_folder, f"Apy/orig_{idx0 + i}.png"))
+
     def svd_based_ddnm_plus(self, model, cls_fn):
         args, config = self.args, self.config
         loader = self._loader()
@@ -588,10 +626,9 @@ class Diffusion(object):
         sigma_y = args.sigma_y
         rank, world = ddist.world_state()      # the INITIALISED group (env-only sharding without a group loses shards)
         print(f"Start from {args.subset_start}")
-        idx_so_far = args.subset_start
-        C, S = config.data.channels, config.data.image_size
+        C, S, batch_size = config.data.channels, config.data.image_size, config.sampling.batch_size
         # DDNM_SAMPLES=NS: every measurement restored NS times in one sampler call, rows [sample k][image j], sample k with
-        # the noise of a run under --seed seed + k and all of them with the one y of this run
+        # the noise of a run under --seed seed + k and all of them with the one y of this run (NS = 1: the plain run)
         NS = samples()
         log = MetricLog(S, NS)
         os.makedirs(os.path.join(args.image_folder, "Apy"), exist_ok=True)      # (rank 0 made the image folder before the first barrier)
@@ -603,172 +640,117 @@ class Diffusion(object):
         # its own images (file names carry the global image index) and the PSNR reduced at the end (splitting a
         # batch of one left N - 1 GPUs idle).  Either way an image's result does not depend on the rank count: its noise is a
         # function of (seed, batch index, image index in the batch) only.
-        deal = world > 1 and config.sampling.batch_size < world
+        deal = world > 1 and batch_size < world
+        split = world > 1 and not deal
+        writer = rank == 0 or deal
         philox = os.environ.get("DDNM_NOISE") != "torch"      # in-kernel Philox draws (default) | ATen tape (BatchNoise)
         # DDNM_FUSE_BATCHES=K: up to K consecutive loader batches of this rank restored in ONE sampler call (per-image
         # noise keys: each image draws what it draws alone); needs whole batches per rank
         K = fuse_batches()
-        fuse = K > 1 and (world == 1 or deal)
-        if K > 1 and not fuse:
-            print(f"[ddnm_amd] DDNM_FUSE_BATCHES={K} ignored: loader batches of {config.sampling.batch_size} images are "
+        if K > 1 and split:
+            print(f"[ddnm_amd] DDNM_FUSE_BATCHES={K} ignored: loader batches of {batch_size} images are "
                   f"split over {world} ranks")
-        group_ends = {g[-1][0] for g in fuse_groups(len(loader.dataset), config.sampling.batch_size, rank, world, K)} \
-            if fuse else set()
-        pending = []
-        # a mask bank (3-D mask.npy): every loader batch gets the operator of ITS images, image i using mask i % N; a
-        # sampler call's operator is a slice (split mode) or the concatenation (fused group) of those
+        # the plan: the loader batches this rank restores, grouped into sampler calls (restored_images reads the same plan)
+        groups = fuse_groups(len(loader.dataset), batch_size, rank, world, K)
+        first = {bi: args.subset_start + start for group in groups for bi, start, _ in group}
+        ends = {group[-1][0] for group in groups}
+        # a mask bank (3-D mask.npy): every operator is built for the images of ITS rows, image i using mask i % N
         bank = A_funcs if isinstance(A_funcs, InpaintingBank) else None
-        calls = iter(restored_images(len(loader.dataset), config.sampling.batch_size, rank, world, K if fuse else 1,
-                                     args.subset_start)) if bank is not None else None
 
-        def finish(x_all, x_orig, idx0):
-            x_all = x_all.contiguous()
-            img, psnr = ops.finalize_psnr(x_all, x_orig)
-            for j in range(x_orig.shape[0]):
-                save_image(img[j], os.path.join(args.image_folder, f"{idx0 + j}_{0}.png"))
-            log.add(x_all, x_orig, psnr, idx0)
-
-        def finish_samples(x_rows, layout, x_orig, idx0):
-            """The NS * b restorations of one loader batch ("samples_major": [k][j] as the sampler leaves them,
-            "images_major": [j][k] after the gather): every sample's PNG, sample 0's lines, then the K-sample figures."""
-            b = x_orig.shape[0]
-            x_rows = x_rows.contiguous()
-            xs = x_rows.view(NS, b, C, S, S) if layout == "samples_major" else x_rows.view(b, NS, C, S, S).transpose(0, 1)
-            psnr_all = []
-            for k in range(NS):
-                x_k = xs[k].contiguous()
-                img, psnr = ops.finalize_psnr(x_k, x_orig)
-                for j in range(b):
-                    save_image(img[j], os.path.join(args.image_folder, f"{idx0 + j}_{k}.png"))
-                if k == 0:
-                    log.add(x_k, x_orig, psnr, idx0)
-                psnr_all.append(psnr)
-            mean_img, std_img, psnr_mean, std_mean = ops.sample_stats(x_rows, b, NS, layout, x_orig)
-            std_shown = (std_img * STD_DISPLAY_GAIN).clamp_(0.0, 1.0)
-            for j in range(b):
-                save_image(mean_img[j], os.path.join(args.image_folder, f"mean/mean_{idx0 + j}.png"))
-                save_image(std_shown[j], os.path.join(args.image_folder, f"std/std_{idx0 + j}.png"))
-            log.add_samples(psnr_mean, torch.stack(psnr_all), std_mean, mean_img, x_orig)
-
-        def restore(x, y_loc, classes, noise, A_funcs, sizes=None):
-            if bank is not None:
-                images = next(calls)
-                if A_funcs.rows != [i % len(bank) for i in sample_rows(images, sizes or [len(images)], NS)]:
-                    raise RuntimeError("sampler call and restored_images disagree about the images of this call")
-            with torch.no_grad():
-                if sigma_y == 0.0:       # noise-free case, DDNM (diffusion.py:587-588)
-                    xs, _ = ddnm_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, cls_fn=cls_fn,
-                                           classes=classes, config=config, noise=noise, return_cpu=False)
-                else:                    # noisy case, DDNM+ (:589-590)
-                    xs, _ = ddnm_plus_diffusion(x, model, self.betas, args.eta, A_funcs, y_loc, sigma_y, cls_fn=cls_fn,
-                                                classes=classes, config=config, noise=noise, return_cpu=False)
-            return xs[0]
-
-        for bi, (x_orig, classes) in enumerate(loader):
-            b = x_orig.shape[0]
-            if deal and bi % world != rank:
-                idx_so_far += b
-                continue
+        def prepare(bi, x_orig):
+            """The Part of loader batch `bi`: y = A x_orig of the whole batch (operators are cheap, and the writer needs
+            A^+ y of all: the Apy/ files), x_T and the noise sources of this rank's images [lo, hi) for every sample."""
+            idx0, b = first[bi], x_orig.shape[0]
             # (split mode: every rank sees the same batch -- same loader seed; rank r restores images [lo, hi) of it)
             x_orig = data_transform(config, x_orig.to(self.device)).contiguous()
-            lo, hi = (0, b) if deal else ddist.shard_range(b, rank, world)
-            writer = deal or rank == 0
+            lo, hi = rank_slice(b, batch_size, rank, world)
             if philox:
-                # no ATen RNG launch in the loop, nothing drawn for other ranks' images: key = (seed, batch), counter =
-                # (element, iteration, image index in the batch); bench.py times this path
-                noise = ops.PhiloxNoise(_mix64(args.seed, bi), image_base=lo)
-                x = noise.tensor(ops.PhiloxNoise.XT_ITER, torch.empty(max(hi - lo, 1), C, S, S, device=self.device))[:hi - lo]
-                parts = [(noise, j) for j in range(hi - lo)]      # (source, image) of every row, for a keyed call
-                if NS > 1:
-                    srcs = sample_sources(args.seed, bi, NS, lo)
-                    like = torch.empty(max(hi - lo, 1), C, S, S, device=self.device)
-                    x = torch.cat([src.tensor(ops.PhiloxNoise.XT_ITER, like)[:hi - lo] for src in srcs], 0)
-                    parts = [(src, j) for src in srcs for j in range(hi - lo)]
+                # no ATen RNG launch in the loop, nothing drawn for other ranks' images: key = (seed + sample, batch),
+                # counter = (element, iteration, image index in the batch); bench.py times this path
+                noise = sample_sources(args.seed, bi, NS, lo)
+                like = torch.empty(max(hi - lo, 1), C, S, S, device=self.device)
+                x_T = _cat([src.tensor(ops.PhiloxNoise.XT_ITER, like)[:hi - lo] for src in noise])
             else:
-                noise = BatchNoise(args.seed, bi, b, (C, S, S), lo, hi, self.device)
-                x = noise.x_T()
-                parts = [noise]                                   # the tapes of a fused call, one per sample
-                if NS > 1:
-                    parts += [BatchNoise(args.seed + k, bi, b, (C, S, S), lo, hi, self.device) for k in range(1, NS)]
-                    x = torch.cat([x] + [t.x_T() for t in parts[1:]], 0)
-            if bank is not None:
-                A_funcs = bank.for_images(range(idx_so_far, idx_so_far + b))
-            y = A_funcs.A(x_orig)                # the whole batch: operators are cheap, and the writer needs A^+ y of all
+                noise = [BatchNoise(args.seed + k, bi, b, (C, S, S), lo, hi, self.device) for k in range(NS)]
+                x_T = _cat([tape.x_T() for tape in noise])
+            A_batch = A_funcs if bank is None else bank.for_images(range(idx0, idx0 + b))
+            y = A_batch.A(x_orig)
             if args.add_noise:
                 if philox:
                     y = y + measurement_noise(_mix64(args.seed, bi) ^ 0x5DEECE66D, y.reshape(b, -1)).reshape(y.shape) * sigma_y
                 else:
-                    y = y + noise.draw(tuple(y.shape)) * sigma_y
-                    for t in parts[1:]:
-                        t.draw(tuple(y.shape))       # the samples share y; each tape still moves as in its own run
+                    y = y + noise[0].draw(tuple(y.shape)) * sigma_y
+                    for tape in noise[1:]:
+                        tape.draw(tuple(y.shape))    # the samples share y; each tape still moves as in its own run
             if writer:
-                Apy = A_funcs.A_pinv(y).view(b, C, S, S)
-                if args.deg[:6] == "deblur":
-                    Apy = y.view(b, C, S, S)
-                elif args.deg == "colorization":
-                    Apy = y.view(b, 1, S, S).repeat(1, 3, 1, 1)
-                elif args.deg == "inpainting":
-                    Apy = Apy + A_funcs.A_pinv(A_funcs.A(torch.ones_like(Apy))).reshape(*Apy.shape) - 1
-                for i in range(b):
-                    save_image(ops.finalize_psnr(Apy[i:i + 1].contiguous())[0][0],
-                               os.path.join(args.image_folder, f"Apy/Apy_{idx_so_far + i}.png"))
-                    save_image(ops.finalize_psnr(x_orig[i:i + 1])[0][0],
-                               os.path.join(args.image_folder, f"Apy/orig_{idx_so_far + i}.png"))
-            if fuse:
-                # whole batches (lo, hi = 0, b): held until the last batch of the group, restored together
-                if NS > 1 and bank is not None:
-                    A_funcs = bank.for_images(list(range(idx_so_far, idx_so_far + b)) * NS)
-                y_rows = y.reshape(b, -1).contiguous()
-                pending.append((x, y_rows.repeat(NS, 1) if NS > 1 else y_rows, classes.repeat(NS) if NS > 1 else classes,
-                                parts, x_orig, idx_so_far, A_funcs))
-                if bi in group_ends:
-                    if philox:
-                        fnoise = ops.KeyedPhiloxNoise.from_sources([pair for p in pending for pair in p[3]])
-                    else:
-                        fnoise = FusedTape([t for p in pending for t in p[3]])
-                    x_fused = restore(torch.cat([p[0] for p in pending], 0), torch.cat([p[1] for p in pending], 0),
-                                      torch.cat([p[2] for p in pending], 0), fnoise,
-                                      A_funcs if bank is None else PerImageInpainting.concat([p[6] for p in pending]),
-                                      [p[4].shape[0] for p in pending])
-                    off = 0
-                    for p in pending:                # one PSNR line per loader batch, in loader order
-                        nb = p[4].shape[0]
-                        if NS > 1:
-                            finish_samples(x_fused[off:off + NS * nb], "samples_major", p[4], p[5])
-                        else:
-                            finish(x_fused[off:off + nb], p[4], p[5])
-                        off += NS * nb
-                    pending = []
-                idx_so_far += b
-                continue
-            if NS > 1:
-                if hi > lo:
-                    x_loc = restore(x, y.reshape(b, -1)[lo:hi].repeat(NS, 1).contiguous(), classes.repeat(NS),
-                                    ops.KeyedPhiloxNoise.from_sources(parts) if philox else FusedTape(parts),
-                                    A_funcs if bank is None else
-                                    bank.for_images(list(range(idx_so_far + lo, idx_so_far + hi)) * NS))
-                else:
-                    x_loc = x                # empty shard: takes part in the gather only
-                if deal or world == 1:
-                    x_all, layout = x_loc, "samples_major"
-                else:
-                    # [k][j] -> one row of K * chw per image, so that the batch still meets in ONE collective; rank 0
-                    # holds [b][K][chw]
-                    rows = x_loc.reshape(NS, hi - lo, C * S * S).transpose(0, 1).reshape(hi - lo, NS * C * S * S)
-                    x_all, layout = ddist.gather_images(rows, n_total=b).reshape(b * NS, C, S, S), "images_major"
-                if writer:
-                    finish_samples(x_all, layout, x_orig, idx_so_far)
-                idx_so_far += b
-                continue
-            if hi > lo:
-                x_loc = restore(x, y.reshape(b, -1)[lo:hi].contiguous(), classes, noise,
-                                A_funcs if bank is None else A_funcs.narrow(lo, hi))
+                self._write_apy(A_batch, y, x_orig, idx0)
+            return Part(bi, idx0, b, lo, hi, x_orig, y.reshape(b, -1)[lo:hi].contiguous(), x_T, noise)
+
+        def restore(parts):
+            """ONE sampler call for the loader batches `parts` (one batch, or a fused group), rows batch-major, then
+            sample, then image (sample_rows); returns the rows of every part."""
+            sizes = [p.hi - p.lo for p in parts]
+            if not any(sizes):                   # empty shard (fewer images than ranks): takes part in the gather only
+                return [p.x_T for p in parts]
+            ys = [p.y.repeat(NS, 1) if NS > 1 else p.y for p in parts]      # the samples of an image share its y
+            if len(parts) == 1 and NS == 1:      # the batch's own source: the unkeyed step kernels, no torch.cat per step
+                noise = parts[0].noise[0]
+            elif philox:
+                noise = ops.KeyedPhiloxNoise.from_sources([(src, j) for p, n in zip(parts, sizes) for src in p.noise
+                                                           for j in range(n)])
             else:
-                x_loc = x                    # empty shard (fewer images than ranks): takes part in the gather only
-            x_all = x_loc if deal else ddist.gather_images(x_loc, n_total=b)      # the path's single collective (one per batch)
-            if writer:
-                finish(x_all, x_orig, idx_so_far)
-            idx_so_far += b
+                noise = FusedTape([tape for p in parts for tape in p.noise])
+            op = A_funcs
+            if bank is not None:
+                images = [i for p in parts for i in range(p.idx0 + p.lo, p.idx0 + p.hi)]
+                op = bank.for_images(sample_rows(images, sizes, NS))
+            x, y = _cat([p.x_T for p in parts]), _cat(ys)
+            # noise-free: DDNM (diffusion.py:587-588); noisy: DDNM+, which takes sigma_y after y (:589-590).  classes=None:
+            # the samplers take the class from the config, like the reference
+            sampler, extra = (ddnm_diffusion, ()) if sigma_y == 0.0 else (ddnm_plus_diffusion, (sigma_y,))
+            with torch.no_grad():
+                xs, _ = sampler(x, model, self.betas, args.eta, op, y, *extra, cls_fn=cls_fn, classes=None, config=config,
+                                noise=noise, return_cpu=False)
+            return torch.split(xs[0], [NS * n for n in sizes])
+
+        def finish(p, x_rows):
+            """The NS * (hi - lo) restorations of part `p`, rows [k][j] as the sampler leaves them: gathered if the batch
+            is split over ranks; then every sample's PNG, sample 0's lines and, for NS > 1, the K-sample figures."""
+            layout = "samples_major"
+            if split:
+                # [k][j] -> one row of NS * chw per image, so that the batch meets in ONE collective (the path's single
+                # one, once per loader batch); every rank then holds [b][NS][chw]
+                n = p.hi - p.lo
+                rows = x_rows.reshape(NS, n, C * S * S).transpose(0, 1).reshape(n, NS * C * S * S)
+                x_rows, layout = ddist.gather_images(rows, n_total=p.b).reshape(p.b * NS, C, S, S), "images_major"
+            if not writer:
+                return
+            x_rows = x_rows.contiguous()
+            xs = x_rows.view(NS, p.b, C, S, S) if layout == "samples_major" else x_rows.view(p.b, NS, C, S, S).transpose(0, 1)
+            psnr_all = []
+            for k in range(NS):
+                x_k = xs[k].contiguous()
+                img, psnr = ops.finalize_psnr(x_k, p.x_orig)
+                for j in range(p.b):
+                    save_image(img[j], os.path.join(args.image_folder, f"{p.idx0 + j}_{k}.png"))
+                if k == 0:
+                    log.add(x_k, p.x_orig, psnr, p.idx0)
+                psnr_all.append(psnr)
+            if NS > 1:
+                mean_img, std_img, psnr_mean, std_mean = ops.sample_stats(x_rows, p.b, NS, layout, p.x_orig)
+                std_shown = (std_img * STD_DISPLAY_GAIN).clamp_(0.0, 1.0)
+                for j in range(p.b):
+                    save_image(mean_img[j], os.path.join(args.image_folder, f"mean/mean_{p.idx0 + j}.png"))
+                    save_image(std_shown[j], os.path.join(args.image_folder, f"std/std_{p.idx0 + j}.png"))
+                log.add_samples(psnr_mean, torch.stack(psnr_all), std_mean, mean_img, p.x_orig)
+
+        group = []
+        for bi, x_orig in ((bi, x) for bi, (x, _) in enumerate(loader) if bi in first):      # the batches of the plan
+            group.append(prepare(bi, x_orig))
+            if bi in ends:
+                for p, x_rows in zip(group, restore(group)):     # one PSNR line per loader batch, in loader order
+                    finish(p, x_rows)
+                group = []
         self.last_metrics = log.total(rank, self.device, reduce=deal)
         ddist.barrier()
         return self.last_metrics["psnr"]
