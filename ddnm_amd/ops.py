@@ -5,6 +5,8 @@ stream; every computation below is a hand-written HIP kernel from
 ddnm_amd/csrc.  Nothing in this module falls back to torch ops.
 """
 import ctypes
+import math
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -85,6 +87,13 @@ def max_launch_batch(per_image_bytes, margin=2):
 # ----------------------------------------------------------------------------- convolution
 CONV_COUT_ALIGN = 128
 
+# Module switches: tests and tools set them ON THE MODULE (monkeypatch / a script's assignment), so every use below reads
+# them at call time.
+_NO_FUSED_GN = False            # A/B profiling: convolutions emit no GroupNorm partials
+FORCE_ONE_TILE = False          # A/B timing: every split-fp16 3x3 launch on the one-tile kernel
+_NO_S16_GATHER = False          # A/B: gather-form launches stay on the fp32 MFMA kernel
+_S16_CHECK = False              # debugging: assert finiteness after every split-fp16 launch (synchronises)
+_F16_PREPASS_MIN_COUT = 256     # first-generation fp16 3x3 launches of at least this many output channels take the GroupNorm pre-pass
 
 _conv_ws = {}
 
@@ -108,11 +117,6 @@ def pack_conv_weight(w, cin_pad=None):
     out = torch.zeros(cout_pad, kh * kw, cin_pad, dtype=torch.float32, device=w.device)
     out[:cout, :, :cin] = w.float().permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
     return out.contiguous()
-
-
-import os as _os
-_NO_FUSED_GN = False      # module attribute (A/B profiling from a script): convolutions emit no GroupNorm partials
-FORCE_ONE_TILE = False    # module attribute (A/B timing from a script): every split-fp16 3x3 launch on the one-tile kernel
 
 
 class Act:
@@ -161,7 +165,6 @@ def s16_weight_scale(*ws):
     """The power of two 2^s that brings max|W| of a launch's weight tensors (3x3 kernel + fused shortcut: they share
     one accumulator) into [2^13, 2^14): fp16 `hi` parts stay far from 65504 and the `lo` parts of all but negligible
     weights are normal fp16 numbers (include/ddnm_hip.h::ddnm_conv3x3_s16_f32)."""
-    import math
     m = max(float(w.abs().max()) for w in ws)
     if not (m > 0.0) or not math.isfinite(m):
         return 1.0
@@ -266,7 +269,6 @@ def conv_runs_s16_gather(B, H, W, cin, cout, ksize=3, stride=1):
 
 
 _S16_ACT_SCALE = None
-_NO_S16_GATHER = False      # module attribute (A/B from a script): gather-form launches stay on the fp32 MFMA kernel
 
 
 def _s16_act_scale():
@@ -283,7 +285,6 @@ def conv_runs_f16(B, H, W, cin, cout, ksize=3):
     return (L.ddnm_conv3x3_f16_supported if ksize == 3 else L.ddnm_conv1x1_f16_supported)(ctypes.byref(d)) == 1
 
 
-_F16_PREPASS_MIN_COUT = 256
 _f16_scratch_buf = {}
 
 
@@ -299,7 +300,6 @@ def _f16_scratch(device, numel, slot=0):
 
 
 AMAX_N = 32          # include/ddnm_hip.h::DDNM_AMAX_N
-_S16_CHECK = False      # module attribute (debugging): assert finiteness after every split-fp16 launch (synchronises)
 
 
 def amax_bound(a0, a1=None):
@@ -323,6 +323,158 @@ def amax_bound(a0, a1=None):
     return out
 
 
+class ConvFamily(NamedTuple):
+    """One kernel family of the convolution launchers.  Entry points are NAMES, resolved on the loaded library at call time."""
+    name: str
+    run: str
+    stats_tiles: Optional[str]          # None: the family emits no GroupNorm partials ...
+    workspace_floats: Optional[str]     # ... / takes no workspace
+    variant: Callable                   # (library, descriptor) -> `KernelTimer` variant label; asked only under a timer
+    pack: str = "f32"                   # which of conv2d's weight packs the launch reads: "f32" / "s16" / "f16"
+    label: str = "ddnm_conv2d"          # what a refused launch is reported under
+    strict: bool = False                # True: a negative planner answer raises under the planner's name; False: the
+    #                                     launch goes on and the launcher refuses the descriptor under `label`
+
+
+def _f32_variant(L, d):
+    kind = "conv3x3_halo_f32" if (d.ksize == 3 and d.stride == 1) else "conv_gather_f32"
+    return kind + {128: "<128x128>", 64: "<64x64>", 32: "<128x32>"}[L.ddnm_conv2d_f32_tile_n(ctypes.byref(d))]
+
+
+def _s16_variant(L, d):
+    persistent = L.ddnm_conv3x3_s16_persistent(ctypes.byref(d)) == 1
+    return "conv3x3_s16_persist<256x128>" if persistent else "conv3x3_halo_s16<256x128>"
+
+
+CONV_FAMILIES = {f.name: f for f in (
+    # the network's 3-channel output convolution: HBM-bound vector-ALU kernel (csrc/conv_small_f32.hip)
+    ConvFamily("small_cout", "ddnm_conv3x3_small_cout_f32", None, None, lambda L, d: "conv3x3_small_cout_f32",
+               label="ddnm_conv3x3_small_cout_f32"),
+    # split-fp16 arithmetic (fp32-grade products on the fp16 matrix pipe): the sub-pixel form of an upsample convolution,
+    # the 3x3 / stride-1 halo kernel, and the per-tap gather form for 1x1 / strided / 8x8-level launches (no fused shortcut)
+    ConvFamily("s16_subpixel", "ddnm_conv3x3_s16_f32", "ddnm_conv3x3_s16_stats_tiles", "ddnm_conv3x3_s16_workspace_floats",
+               lambda L, d: "conv2x2x4_s16_subpixel<256x128>", pack="s16"),
+    ConvFamily("s16", "ddnm_conv3x3_s16_f32", "ddnm_conv3x3_s16_stats_tiles", "ddnm_conv3x3_s16_workspace_floats",
+               _s16_variant, pack="s16"),
+    ConvFamily("s16_gather", "ddnm_conv_gather_s16_f32", "ddnm_conv_gather_s16_stats_tiles",
+               "ddnm_conv_gather_s16_workspace_floats", lambda L, d: "conv_gather_s16", pack="s16"),
+    # first-generation fp16-operand engine (the reference's use_fp16 torso): halo kernel, and one GEMM (1x1, im2col'd 3x3)
+    ConvFamily("f16_3x3", "ddnm_conv3x3_f16_f32", "ddnm_conv3x3_f16_stats_tiles", "ddnm_conv3x3_f16_workspace_floats",
+               lambda L, d: "conv3x3_halo_f16<256x128>", pack="f16"),
+    ConvFamily("f16_1x1", "ddnm_conv1x1_f16_f32", "ddnm_conv1x1_f16_stats_tiles", "ddnm_conv1x1_f16_workspace_floats",
+               lambda L, d: "conv1x1_f16<256x128>", pack="f16"),
+    # exact fp32: everything else
+    ConvFamily("f32", "ddnm_conv2d_f32", "ddnm_conv2d_f32_stats_tiles", "ddnm_conv2d_f32_workspace_floats", _f32_variant),
+    # fp16-activation path (csrc/conv16.hip; descriptor: Conv16Desc)
+    ConvFamily("conv16", "ddnm_conv16", "ddnm_conv16_stats_tiles", "ddnm_conv16_workspace_floats",
+               lambda L, d: f"conv16<{d.ksize}x{d.ksize}>", pack="h16", label="ddnm_conv16", strict=True),
+    ConvFamily("conv16_out", "ddnm_conv16", None, None, lambda L, d: "conv16<out>", pack="h16", label="ddnm_conv16(out)"),
+)}
+
+
+def _desc_copy(d, **fields):
+    """A copy of descriptor `d` with `fields` replaced: what a planner is asked about an alternative form of the launch."""
+    c = type(d).from_buffer_copy(d)
+    for k, v in fields.items():
+        setattr(c, k, v)
+    return c
+
+
+def _f16_im2col(L, d, src0, src1, gn_silu):
+    """Lowest-resolution 3x3 launches of the first-generation engine (a 256-pixel tile would span several images): im2col
+    with the GroupNorm prologue, then ONE fp16 GEMM with K = 9*Cin -- the (O,ky,kx,I)-packed weights are its matrix.
+    Returns the GEMM's descriptor once the im2col launch is issued, None when the launch does not qualify."""
+    B, Hs, Ws, _ = src0.shape
+    if d.stride != 1 or d.ups or d.skip0 or d.out_nchw or d.res_ups or Hs * Ws >= 256 or (d.C0 | d.C1) % 8:
+        return None
+    cin = d.C0 + d.C1
+    g = _desc_copy(d, ksize=1, pad=0, C0=9 * cin, C1=0, gn_scale=None, gn_shift=None)
+    if L.ddnm_conv1x1_f16_supported(ctypes.byref(g)) != 1:
+        return None
+    col = _f16_scratch(src0.device, B * Hs * Ws * 9 * cin, slot=1)
+    check(L.ddnm_im2col3x3_f16(_p(src0), _p(src1), d.gn_scale, d.gn_shift, col.data_ptr(), B, Hs, Ws, d.C0, d.C1,
+                               int(gn_silu), _stream()), "ddnm_im2col3x3_f16")
+    g.src0, g.src1, g.src_f16 = col.data_ptr(), None, 1
+    return g
+
+
+def _f16_gn_prepass(L, d, src0, src1, gn_silu):
+    """GroupNorm (+ swish) once per element into an fp16 scratch tensor instead of once per (128-output-channel tile x
+    halo overlap) inside the conv's loader; returns the descriptor that reads the scratch tensor."""
+    B, Hs, Ws, _ = src0.shape
+    cin = d.C0 + d.C1
+    h16 = _f16_scratch(src0.device, B * Hs * Ws * cin)
+    check(L.ddnm_gn_apply_f16(_p(src0), _p(src1), d.gn_scale, d.gn_shift, h16.data_ptr(), B, Hs * Ws, d.C0, d.C1,
+                              int(gn_silu), _stream()), "ddnm_gn_apply_f16")
+    return _desc_copy(d, src0=h16.data_ptr(), src1=None, C0=cin, C1=0, gn_scale=None, gn_shift=None, src_f16=1)
+
+
+def _select_f16(L, d, src0, src1, gn, gn_silu):
+    """The first-generation fp16-operand engine's part of _select_conv_family (packed fp16 weights are on offer): the
+    halo kernel or the GEMM where the shape qualifies, with their pre-passes issued; the exact-fp32 kernels otherwise."""
+    fam, launch = CONV_FAMILIES["f32"], d
+    if d.ksize == 3:
+        if L.ddnm_conv3x3_f16_supported(ctypes.byref(d)) == 1:
+            fam = CONV_FAMILIES["f16_3x3"]
+        else:
+            g = _f16_im2col(L, d, src0, src1, gn_silu)
+            if g is not None:
+                return CONV_FAMILIES["f16_1x1"], g, None          # (the im2col launch has applied the GroupNorm)
+    elif d.ksize == 1 and not d.skip0:
+        g = _desc_copy(d, gn_scale=None, gn_shift=None)           # the GEMM kernel has no fused prologue: always the pre-pass
+        if L.ddnm_conv1x1_f16_supported(ctypes.byref(g)) == 1:
+            fam, launch = CONV_FAMILIES["f16_1x1"], g
+    if fam.pack == "f16" and gn is not None and (fam.name == "f16_1x1" or d.Cout >= _F16_PREPASS_MIN_COUT):
+        launch = _f16_gn_prepass(L, d, src0, src1, gn_silu)
+    return fam, launch, gn
+
+
+def _select_conv_family(L, d, src0, src1, gn, gn_silu, weight_s16, weight_f16):
+    """The kernel family of the filled descriptor `d`, given the packs on offer -> (family, descriptor to launch, the
+    GroupNorm affine the launch still applies).  Precedence: small_cout; the split-fp16 families (sub-pixel or 3x3, then
+    gather); with `weight_f16` the first-generation engine INSTEAD of those; exact fp32.  Every planner sees `d` as the
+    launch will: the fused-shortcut fields are filled (some planners key on the pointer, some on the channel counts; ADVICE
+    r3 / r4) and `weight` is still the fp32 pack -- the chosen pack's pointers are set by conv2d afterwards."""
+    q, fused = ctypes.byref(d), bool(d.skip0)
+    if (d.out_nchw and d.Cout <= 4 and not fused and weight_f16 is None
+            and L.ddnm_conv3x3_small_cout_f32_supported(q) == 1):
+        return CONV_FAMILIES["small_cout"], d, gn
+    if weight_f16 is not None:
+        return _select_f16(L, d, src0, src1, gn, gn_silu)
+    if weight_s16 is not None:
+        if d.flags == UPS_SUBPIXEL:                               # (conv2d has checked that the launch qualifies)
+            return CONV_FAMILIES["s16_subpixel"], d, gn
+        if (d.ksize == 3 and d.stride == 1
+                and (not fused or (weight_s16[2] is not None and gn is not None and d.SC0 % 32 == 0 and d.SC1 % 32 == 0))
+                and L.ddnm_conv3x3_s16_supported(q) == 1):
+            return CONV_FAMILIES["s16"], d, gn
+        if not fused and not _NO_S16_GATHER and L.ddnm_conv_gather_s16_supported(q) == 1:
+            return CONV_FAMILIES["s16_gather"], d, gn
+    return CONV_FAMILIES["f32"], d, gn
+
+
+def _launch_conv(L, fam, d, out, emit_stats, record):
+    """The tail of every convolution launch: the GroupNorm-partials tensor where the plan emits them, the split-K
+    workspace, the checked launch -> Act(out, stats, tiles)."""
+    stats, tiles = None, 0
+    if emit_stats and fam.stats_tiles is not None:
+        tiles = getattr(L, fam.stats_tiles)(ctypes.byref(d))
+        if tiles < 0 and fam.strict:
+            check(tiles, fam.stats_tiles)
+        if tiles > 0:
+            stats = torch.empty(d.B * tiles * d.Cout * 2, dtype=torch.float32, device=out.device)
+            d.stats_out = stats.data_ptr()
+    if fam.workspace_floats is not None:
+        need = getattr(L, fam.workspace_floats)(ctypes.byref(d))
+        if need < 0 and fam.strict:
+            check(int(need), fam.workspace_floats)
+        if need > 0:
+            ws = _conv_workspace(out.device, need)
+            d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
+    _launch(getattr(L, fam.run), d, fam.label, record)
+    return Act(out, stats, tiles)
+
+
 def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_stride=0, res=None, res_ups=False,
            gn=None, gn_silu=True, stride=1, pad=None, ups=False, out=None, out_nchw=False, out_hw=None, tile=0,
            emit_stats=False, weight_f16=None, skip=None, skip_weight=None, skip_weight_f16=None, weight_s16=None,
@@ -333,6 +485,7 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     one_tile=True: the split-fp16 3x3 launch runs the one-tile-per-workgroup kernel where the persistent form would apply
     (same results bit for bit; A/B timing and the bit-identity tests).
     With emit_stats=True returns an `Act` (tensor + GroupNorm partials when the launch can produce them).
+    weight_f16 (packed fp16 weights): the fp16-operand MFMA path (the reference's use_fp16 torso) where the shape qualifies.
     weight_s16 = (packed, scale, packed_skip or None) from pack_conv_weight_s16: 3x3 / stride-1 launches whose shape
     qualifies then run the split-fp16 kernel (fp32-grade products on the fp16 matrix pipe) instead of the fp32 one.
     Operands such a launch reads RAW (no GroupNorm: the main operand when gn is None, the fused shortcut's input always)
@@ -345,10 +498,7 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     Hin, Win = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
     if pad is None:
         pad = ksize // 2
-    if out_hw is None:
-        Ho, Wo = (Hin // stride, Win // stride)
-    else:
-        Ho, Wo = out_hw
+    Ho, Wo = (Hin // stride, Win // stride) if out_hw is None else out_hw
     if out is None:
         shape = (B, cout, Ho, Wo) if out_nchw else (B, Ho, Wo, cout)
         out = torch.empty(shape, dtype=torch.float32, device=src0.device)
@@ -361,37 +511,20 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
     d.ksize, d.stride, d.pad, d.Ho, d.Wo = ksize, stride, pad, Ho, Wo
     d.ups, d.gn_silu, d.out_nchw = int(ups), int(gn_silu), int(out_nchw)
     d.badd_stride, d.tile, d.res_ups = badd_stride, tile, int(res_ups)
-    d.flags = 1 if (one_tile or FORCE_ONE_TILE) else 0
-    L = _lib.lib()
-    if ups_subpixel:
-        d.flags = UPS_SUBPIXEL
-        if (not ups or weight_s16 is None or weight_f16 is not None or skip is not None
-                or L.ddnm_conv3x3_s16_ups_subpixel_supported(ctypes.byref(d)) != 1):
-            raise ValueError(f"ups_subpixel: launch (B={B}, {Hs}x{Ws} -> {Ho}x{Wo}, Cin={C0 + C1}, Cout={cout}) does not "
-                             "qualify (ddnm_conv3x3_s16_ups_subpixel_supported)")
-    if out_nchw and cout <= 4 and skip is None and weight_f16 is None and L.ddnm_conv3x3_small_cout_f32_supported(ctypes.byref(d)) == 1:
-        # the network's 3-channel output convolution: HBM-bound vector-ALU kernel (csrc/conv_small_f32.hip)
-        _launch(L.ddnm_conv3x3_small_cout_f32, d, "ddnm_conv3x3_small_cout_f32",
-                lambda: ("conv3x3_small_cout_f32", 2.0 * B * Ho * Wo * cout * 9 * C0,
-                         (B, Ho, Wo, C0, cout, 3, 1, 0, 0, gn is not None, False)))
-        return Act(out, None, 0) if emit_stats else out
-    # fp16-operand MFMA path (the reference's use_fp16 torso) when packed fp16 weights are supplied and the
-    # shape qualifies; everything else runs the exact-fp32 kernels
-    f16, f16_1x1 = False, False
+    d.flags = UPS_SUBPIXEL if ups_subpixel else (1 if (one_tile or FORCE_ONE_TILE) else 0)
     if skip is not None:
-        # the whole shortcut part of the descriptor is filled BEFORE the support queries below, so that every planner
-        # sees the descriptor the launch will see (some key on the pointer, some on the channel counts);
-        # skip_weight is chosen further down, once the kernel family is known
+        # fused 1x1 shortcut (the caller has checked `conv_fuses_skip`): filled BEFORE any support query; its weight
+        # pointer follows below, once the kernel family is known
         s0, s1 = tensor_of(skip[0]), tensor_of(skip[1])
         d.skip0, d.skip1 = _p(s0), _p(s1)
         d.SC0, d.SC1 = s0.shape[3], (0 if s1 is None else s1.shape[3])
-    s16 = ups_subpixel or (weight_s16 is not None and weight_f16 is None and ksize == 3 and stride == 1
-           and (skip is None or (weight_s16[2] is not None and gn is not None and d.SC0 % 32 == 0 and d.SC1 % 32 == 0))
-           and L.ddnm_conv3x3_s16_supported(ctypes.byref(d)) == 1)
-    # ... and the per-tap gather form of the same arithmetic for 1x1 / strided / 8x8-level launches (no fused shortcut)
-    s16g = (not s16 and weight_s16 is not None and weight_f16 is None and skip is None and not _NO_S16_GATHER
-            and L.ddnm_conv_gather_s16_supported(ctypes.byref(d)) == 1)
-    if s16 or s16g:
+    L = _lib.lib()
+    if ups_subpixel and (not ups or weight_s16 is None or weight_f16 is not None or skip is not None
+                         or L.ddnm_conv3x3_s16_ups_subpixel_supported(ctypes.byref(d)) != 1):
+        raise ValueError(f"ups_subpixel: launch (B={B}, {Hs}x{Ws} -> {Ho}x{Wo}, Cin={C0 + C1}, Cout={cout}) does not "
+                         "qualify (ddnm_conv3x3_s16_ups_subpixel_supported)")
+    fam, d, gn = _select_conv_family(L, d, src0, src1, gn, gn_silu, weight_s16, weight_f16)
+    if fam.pack == "s16":
         d.weight = weight_s16[0].data_ptr()
         d.acc_scale = 1.0 / (float(weight_s16[1]) * _s16_act_scale())
         if gn is None or skip is not None:
@@ -400,94 +533,25 @@ def conv2d(src0, weight, cout, ksize, *, src1=None, bias=None, badd=None, badd_s
             if raw_amax is None:
                 raw_amax = amax_bound(*skip) if skip is not None else amax_bound(a_src0, a_src1)
             d.amax_in = raw_amax.data_ptr()
-    if weight_f16 is not None:
-        if ksize == 3:
-            f16 = L.ddnm_conv3x3_f16_supported(ctypes.byref(d)) == 1
-            if (not f16 and stride == 1 and not ups and skip is None and not out_nchw and not res_ups
-                    and Hs * Ws < 256 and (C0 | C1) % 8 == 0):
-                # lowest-resolution level (a 256-pixel tile would span several images): im2col with the GroupNorm
-                # prologue, then ONE fp16 GEMM with K = 9*Cin -- the (O,ky,kx,I)-packed weights are its matrix
-                d.ksize, d.pad, d.C0, d.C1, d.gn_scale, d.gn_shift = 1, 0, 9 * (C0 + C1), 0, None, None
-                if L.ddnm_conv1x1_f16_supported(ctypes.byref(d)) == 1:
-                    col = _f16_scratch(src0.device, B * Hs * Ws * 9 * (C0 + C1), slot=1)
-                    check(L.ddnm_im2col3x3_f16(_p(src0), _p(src1), None if gn is None else _p(gn[0]),
-                                               None if gn is None else _p(gn[1]), col.data_ptr(), B, Hs, Ws, C0, C1,
-                                               int(gn_silu), _stream()), "ddnm_im2col3x3_f16")
-                    d.src0, d.src1, d.src_f16 = col.data_ptr(), None, 1
-                    f16 = f16_1x1 = True
-                    gn = None
-                else:
-                    d.ksize, d.pad, d.C0, d.C1 = 3, pad, C0, C1
-                    d.gn_scale, d.gn_shift = (None, None) if gn is None else (_p(gn[0]), _p(gn[1]))
-        elif ksize == 1 and skip is None:
-            d.gn_scale, d.gn_shift = None, None         # the GEMM kernel has no fused prologue: always the pre-pass
-            f16 = f16_1x1 = L.ddnm_conv1x1_f16_supported(ctypes.byref(d)) == 1
-            if not f16 and gn is not None:
-                d.gn_scale, d.gn_shift = _p(gn[0]), _p(gn[1])
-    if f16:
+    elif fam.pack == "f16":
         d.weight = weight_f16.data_ptr()
-        if gn is not None and (f16_1x1 or cout >= _F16_PREPASS_MIN_COUT):
-            # GroupNorm (+ swish) once per element into an fp16 scratch tensor instead of once per
-            # (128-output-channel tile x halo overlap) inside the conv's loader
-            h16 = _f16_scratch(src0.device, B * Hs * Ws * (C0 + C1))
-            check(L.ddnm_gn_apply_f16(_p(src0), _p(src1), _p(gn[0]), _p(gn[1]), h16.data_ptr(), B, Hs * Ws, C0, C1,
-                                      int(gn_silu), _stream()), "ddnm_gn_apply_f16")
-            d.src0, d.src1, d.C0, d.C1 = h16.data_ptr(), None, C0 + C1, 0
-            d.gn_scale, d.gn_shift, d.src_f16 = None, None, 1
     if skip is not None:
-        # fused 1x1 shortcut; the caller has checked `conv_fuses_skip` (3x3 halo launch)
-        d.skip_weight = _p(skip_weight_f16) if f16 else (weight_s16[2].data_ptr() if s16 else _p(skip_weight))
-        if f16 and skip_weight_f16 is None:
+        if fam.pack == "f16" and skip_weight_f16 is None:
             raise ValueError("fp16 launch with a fused shortcut needs skip_weight_f16")
-    if f16_1x1:
-        fn_run, fn_tiles, fn_ws = L.ddnm_conv1x1_f16_f32, L.ddnm_conv1x1_f16_stats_tiles, L.ddnm_conv1x1_f16_workspace_floats
-    elif f16:
-        fn_run, fn_tiles, fn_ws = L.ddnm_conv3x3_f16_f32, L.ddnm_conv3x3_f16_stats_tiles, L.ddnm_conv3x3_f16_workspace_floats
-    elif s16:
-        fn_run, fn_tiles, fn_ws = L.ddnm_conv3x3_s16_f32, L.ddnm_conv3x3_s16_stats_tiles, L.ddnm_conv3x3_s16_workspace_floats
-    elif s16g:
-        fn_run, fn_tiles, fn_ws = (L.ddnm_conv_gather_s16_f32, L.ddnm_conv_gather_s16_stats_tiles,
-                                   L.ddnm_conv_gather_s16_workspace_floats)
-    else:
-        fn_run, fn_tiles, fn_ws = L.ddnm_conv2d_f32, L.ddnm_conv2d_f32_stats_tiles, L.ddnm_conv2d_f32_workspace_floats
-    stats, tiles = None, 0
-    if emit_stats and not _NO_FUSED_GN:
-        tiles = fn_tiles(ctypes.byref(d))
-        if tiles > 0:
-            stats = torch.empty(B * tiles * cout * 2, dtype=torch.float32, device=src0.device)
-            d.stats_out = stats.data_ptr()
-    need = fn_ws(ctypes.byref(d))
-    if need > 0:
-        ws = _conv_workspace(src0.device, need)
-        d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
+        d.skip_weight = _p(skip_weight_f16 if fam.pack == "f16" else weight_s16[2] if fam.pack == "s16" else skip_weight)
 
     def record():
-        if f16_1x1:
-            variant = "conv1x1_f16<256x128>"
-        elif f16:
-            variant = "conv3x3_halo_f16<256x128>"
-        elif s16:
-            variant = ("conv2x2x4_s16_subpixel<256x128>" if ups_subpixel else
-                       "conv3x3_s16_persist<256x128>" if L.ddnm_conv3x3_s16_persistent(ctypes.byref(d)) == 1 else "conv3x3_halo_s16<256x128>")
-        elif s16g:
-            variant = "conv_gather_s16"
-        else:
-            tn = L.ddnm_conv2d_f32_tile_n(ctypes.byref(d))
-            kind = "conv3x3_halo_f32" if (ksize == 3 and stride == 1) else "conv_gather_f32"
-            variant = kind + {128: "<128x128>", 64: "<64x64>", 32: "<128x32>"}[tn]
         flops = 2.0 * B * Ho * Wo * cout * (ksize * ksize * (C0 + C1) + d.SC0 + d.SC1)      # + fused 1x1 shortcut
         if ups_subpixel:
             flops *= 16.0 / 36.0                       # 4 of 9 taps per output pixel: the FLOPs the launch issues
-        return variant, flops, (B, Ho, Wo, C0 + C1, cout, ksize, stride, int(ups), d.SC0 + d.SC1, gn is not None,
-                                res is not None)
-    _launch(fn_run, d, "ddnm_conv2d", record)
-    if _S16_CHECK and (s16 or s16g) and not bool(torch.isfinite(out).all()):
+        return fam.variant(L, d), flops, (B, Ho, Wo, C0 + C1, cout, ksize, stride, int(ups), d.SC0 + d.SC1, gn is not None,
+                                          res is not None)
+    act = _launch_conv(L, fam, d, out, emit_stats and not _NO_FUSED_GN, record)
+    if _S16_CHECK and fam.pack == "s16" and not bool(torch.isfinite(out).all()):
         raise FloatingPointError(f"split-fp16 launch produced non-finite values (B={B}, {Hin}x{Win}, Cin={C0 + C1}, "
                                  f"Cout={cout}, k={ksize}): an operand left fp16 range; DDNM_CONV_F32=mfma32 selects the "
                                  "all-fp32 engine")
-    if emit_stats:
-        return Act(out, stats, tiles)
-    return out
+    return act if emit_stats else out
 
 
 # ----------------------------------------------------------------------------- fp16-activation path (csrc/conv16.hip)
@@ -513,8 +577,8 @@ def pack_conv_weight16(w, cin_pad=None):
     return out.contiguous()
 
 
-def _conv16_desc(src, weight, cout, ksize, H, W, ups, skip, skip_weight, bias, res, res_ups, src1=None, gn=None,
-                 gn_silu=True):
+def _conv16_desc(src, weight, cout, ksize, *, H, W, ups=False, skip=None, skip_weight=None, bias=None, res=None,
+                 res_ups=False, src1=None, gn=None, gn_silu=True):
     B = src.shape[0]
     d = Conv16Desc()
     d.src, d.weight, d.bias, d.res = _p(_f16c(src, "src")), _p(_f16c(weight, "weight")), _p(bias), _p(res)
@@ -550,7 +614,8 @@ def conv16(src, weight, cout, ksize, *, src1=None, gn=None, gn_silu=True, bias=N
     H, W = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
     if skip is not None:
         skip = tuple(tensor_of(s) for s in skip)
-    d = _conv16_desc(src, weight, cout, ksize, H, W, ups, skip, skip_weight, bias, res, res_ups, src1, gn, gn_silu)
+    d = _conv16_desc(src, weight, cout, ksize, H=H, W=W, ups=ups, skip=skip, skip_weight=skip_weight, bias=bias, res=res,
+                     res_ups=res_ups, src1=src1, gn=gn, gn_silu=gn_silu)
     L = _lib.lib()
     if out is None:
         out = torch.empty(B, H, W, cout, dtype=torch.float16, device=src.device)
@@ -567,24 +632,13 @@ def conv16(src, weight, cout, ksize, *, src1=None, gn=None, gn_silu=True, bias=N
             d.fin_gamma = None
         else:
             ws.generation += 1
-    stats, tiles = None, 0
-    if emit_stats:
-        tiles = L.ddnm_conv16_stats_tiles(ctypes.byref(d))
-        if tiles < 0:
-            check(tiles, "ddnm_conv16_stats_tiles")
-        if tiles > 0:
-            stats = torch.empty(B * tiles * cout * 2, dtype=torch.float32, device=src.device)
-            d.stats_out = stats.data_ptr()
-    need = L.ddnm_conv16_workspace_floats(ctypes.byref(d))
-    if need < 0:
-        check(int(need), "ddnm_conv16_workspace_floats")
-    if need > 0:
-        ws = _conv_workspace(src.device, need)
-        d.workspace, d.workspace_floats = ws.data_ptr(), ws.numel()
-    _launch(L.ddnm_conv16, d, "ddnm_conv16",
-            lambda: (f"conv16<{ksize}x{ksize}>", 2.0 * B * H * W * cout * (ksize * ksize * d.Cin + d.SC0 + d.SC1),
-                     (B, H, W, d.Cin, cout, ksize, 1, int(ups), d.SC0 + d.SC1, False, res is not None)))
-    return Act(out, stats, tiles, gn=(fin[6].scale, fin[6].shift, fin[0], fin[6], fin[6].generation) if fused_fin else None)
+    fam = CONV_FAMILIES["conv16"]
+    act = _launch_conv(L, fam, d, out, emit_stats,
+                       lambda: (fam.variant(L, d), 2.0 * B * H * W * cout * (ksize * ksize * d.Cin + d.SC0 + d.SC1),
+                                (B, H, W, d.Cin, cout, ksize, 1, int(ups), d.SC0 + d.SC1, False, res is not None)))
+    if fused_fin:
+        act.gn = (fin[6].scale, fin[6].shift, fin[0], fin[6], fin[6].generation)
+    return act
 
 
 def conv16_out(src, weight, cout, bias=None, gn=None, gn_silu=True):
@@ -592,12 +646,13 @@ def conv16_out(src, weight, cout, bias=None, gn=None, gn_silu=True):
     `gn` = (scale, shift) fuses the GroupNorm affine + swish of `out.0/out.1` into its loader like `conv16`."""
     src = tensor_of(src)
     B, H, W, _ = src.shape
-    d = _conv16_desc(src, weight, cout, 3, H, W, False, None, None, bias, None, False, None, gn, gn_silu)
+    d = _conv16_desc(src, weight, cout, 3, H=H, W=W, bias=bias, gn=gn, gn_silu=gn_silu)
     d.out_nchw_f32 = 1
     out = torch.empty(B, cout, H, W, dtype=torch.float32, device=src.device)
     d.out = out.data_ptr()
-    _launch(_lib.lib().ddnm_conv16, d, "ddnm_conv16(out)",
-            lambda: ("conv16<out>", 2.0 * B * H * W * cout * 9 * d.Cin, (B, H, W, d.Cin, cout, 3, 1, 0, 0, False, False)))
+    L, fam = _lib.lib(), CONV_FAMILIES["conv16_out"]
+    _launch_conv(L, fam, d, out, False, lambda: (fam.variant(L, d), 2.0 * B * H * W * cout * 9 * d.Cin,
+                                                 (B, H, W, d.Cin, cout, 3, 1, 0, 0, False, False)))
     return out
 
 

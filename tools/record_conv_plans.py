@@ -22,7 +22,6 @@ import json
 import os
 import struct
 import sys
-import types
 
 import torch
 
@@ -89,32 +88,11 @@ class Capture:
 
 
 def mode_descs(seen):
-    import bench
     import dry_run
-    from ddnm_amd import ops
-    from ddnm_amd.guided_diffusion.models import Model
-    from ddnm_amd.guided_diffusion.unet import create_model
     dry = dry_run.install()
     _lib._lib = Capture(dry, seen)
-    torch.cuda.current_stream = lambda *a: types.SimpleNamespace(cuda_stream=0)      # (the networks key their scratch on it)
-    ops.amax_bound = lambda a0, a1=None: torch.empty(ops.tensor_of(a0).shape[0] * ops.AMAX_N)      # (a launch: stubbed anyway)
-    cel = Model(bench.make_config(), device="cpu")
-    cel.load_state_dict(cel.random_state_dict(1234))
-    for B in BATCHES:                                                           # celeba_b8, celeba_b1
-        cel(torch.empty(B, 3, 256, 256), torch.full((B,), 500.0))
-    for kind in ("fp32", "h16", "gen1"):                                        # adm_fp32, adm_h16, adm_gen1
-        os.environ["DDNM_ADM_GEN1"] = "1" if kind == "gen1" else "0"
-        adm = create_model(image_size=256, num_channels=256, num_res_blocks=2, attention_resolutions="32,16,8",
-                           num_head_channels=64, learn_sigma=True, use_scale_shift_norm=True, resblock_updown=True)
-        adm.device = torch.device("cpu")
-        adm.load_state_dict(adm.random_state_dict(1))
-        if kind != "fp32":
-            adm.convert_to_fp16()
-        for B in BATCHES:
-            adm(torch.empty(B, 3, 256, 256), torch.full((B,), 500.0))
-    for kind in ("fp32", "h16", "gen1"):                                        # cls_fp32, cls_h16, cls_gen1
-        for B in BATCHES:
-            dry_run.classifier(B=B, size=256, kind=kind)
+    for _, _, run in dry_run.engine_modes(BATCHES):
+        run()
 
 
 # ---------------------------------------------------------------------------------------------- corpus: the edge grid
