@@ -255,6 +255,15 @@ __device__ __forceinline__ void split_store(_Float16* dst, f32x4 v) {      // un
 // two that brings the bound into [2^14, 2^15).  `down_only`: the raw operand shares its accumulator with a GroupNorm'd
 // one (fused shortcut), which is O(1): scale down for huge inputs, never up.  The exponent is clamped so that the scale,
 // its inverse and their product with acc_scale stay normal numbers; an all-zero (or non-finite) operand needs no care.
+// s16_scale_from_bound: the scale of a bound word `m` (wave-uniform), however the kernel fetched it (s16_tile.h: one buffer load).
+__device__ __forceinline__ void s16_scale_from_bound(unsigned m, bool down_only, float& scale, float& inv_scale) {
+    int e = (int)((m >> 23) & 0xffu);                 // biased exponent of the bound (sign bit is 0)
+    e = e < 47 ? 47 : (e > 207 ? 207 : e);            // 2^-80 ... 2^80
+    int k = 14 - (e - 127);
+    if (down_only && k > 0) k = 0;
+    scale = __uint_as_float((unsigned)(127 + k) << 23);
+    inv_scale = __uint_as_float((unsigned)(127 - k) << 23);
+}
 __device__ __forceinline__ void s16_operand_scale(const float* __restrict__ amax_in, int img, bool down_only,
                                                   float& scale, float& inv_scale) {
     scale = inv_scale = 1.f;
@@ -263,13 +272,7 @@ __device__ __forceinline__ void s16_operand_scale(const float* __restrict__ amax
     unsigned m = 0u;
 #pragma unroll
     for (int i = 0; i < DDNM_AMAX_N; ++i) m = w[i] > m ? w[i] : m;
-    m = __builtin_amdgcn_readfirstlane(m);
-    int e = (int)((m >> 23) & 0xffu);                 // biased exponent of the bound (sign bit is 0)
-    e = e < 47 ? 47 : (e > 207 ? 207 : e);            // 2^-80 ... 2^80
-    int k = 14 - (e - 127);
-    if (down_only && k > 0) k = 0;
-    scale = __uint_as_float((unsigned)(127 + k) << 23);
-    inv_scale = __uint_as_float((unsigned)(127 - k) << 23);
+    s16_scale_from_bound(__builtin_amdgcn_readfirstlane(m), down_only, scale, inv_scale);
 }
 
 __device__ __forceinline__ f32x4 gn_act(f32x4 v, const f32x4 gsc, const f32x4 gsh, int silu) {

@@ -14,10 +14,9 @@
 // and the B tile [BN][hi 32 | lo 32] arrives by LDS-DMA two steps ahead (unpadded swizzled image, three buffers); all
 // requests are counted (`s_waitcnt vmcnt(N)`, raw barriers): these launches are chains of L2 / HBM round trips.
 // Split-K over channel chunks for launches that cannot fill the chip.
-#include "conv_common.h"
+#include "s16_tile.h"
 
-constexpr int GS_KC = 32;            // channels per chunk
-constexpr int GS_LDH = 72;           // LDS row pitch in halfs: [hi 32 | lo 32 | pad 8] = 144 B
+constexpr int GS_KC = S16_KCH, GS_LDH = S16_LDH;      // channels per chunk, LDS row pitch in halfs: the split forms' own
 
 template <int WM, int WN, int MT, int NT>
 __global__ __launch_bounds__(256) void conv_gather_s16_kernel(const ConvArgs p) {
@@ -54,31 +53,24 @@ __global__ __launch_bounds__(256) void conv_gather_s16_kernel(const ConvArgs p) 
     }
     // ---- weight tile of step (chunk, tap) -> Bs[buf] by LDS-DMA (the weights are the cold stream of these launches: at
     // 8 x 8 / 16 x 16 every weight byte is used by a handful of pixel tiles and comes from HBM, so the tile of step + 2 is
-    // requested while step is multiplied).  One instruction moves 8 rows x 128 B; lane -> (row = 8 g + lane / 8, piece
-    // lane % 8) and FETCHES piece ^ swizzle(row); rows of wave w: 8 w + lrow + 32 j, so (row >> 1) & 7 = 4 (w & 1) + (lrow >> 1).
+    // requested while step is multiplied), in the swizzled lane-linear image of s16_tile.h.
     // Split packing: a row is ntaps * Cin * 4 bytes, (tap, chunk) starts at (tap * Cin + chunk * 32) * 4.
-    const int lrow = lane >> 3, lpiece = lane & 7;
-    const int wswz = (((wave & 1) << 2) | (lrow >> 1));
+    const int lrow = lane >> 3, lpiece = lane & 7;      // the lane's row / 16-byte piece within one LDS-DMA instruction
+    const int wswz = S16_W_SWZ(wave, lrow);
     const unsigned w_rowlen = (unsigned)p.ntaps * (unsigned)p.Cin * 4u;
     const int cout_pad = (d.Cout + 127) / 128 * 128;
     const __amdgpu_buffer_rsrc_t r_w = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.weight)), 0, (unsigned)cout_pad * w_rowlen, 0x00020000);
-    const unsigned w_voff = (unsigned)(n_tile * BN + wave * 8 + lrow) * w_rowlen + (unsigned)((lpiece ^ wswz) * 16);
+    const unsigned w_voff = S16_W_LANE(n_tile * BN + wave * 8 + lrow, w_rowlen, lpiece, wswz);
     auto issue_b = [&](int it, int buf) {
         const int chunk = it / p.ntaps, tap = it - chunk * p.ntaps;
-        char* dst = Bs + buf * WTILE + wave * 1024;
-        const unsigned so = ((unsigned)tap * p.Cin + (unsigned)chunk * GS_KC) * 4u;
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_w, (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, w_voff,
-                                                     so + (unsigned)j * 32u * w_rowlen, 0, 0);
+        s16_w_request<BR, 4>(r_w, Bs + buf * WTILE + wave * 1024, w_voff, ((unsigned)tap * p.Cin + (unsigned)chunk * GS_KC) * 4u, w_rowlen);
     };
 
     // ---- A tile: gathered through registers TWO steps ahead (two register sets used in turn).  Buffer loads with an
     // out-of-range offset for padding (the load returns zero) and GroupNorm vectors fetched unconditionally (a dummy
     // address without GroupNorm): every call issues EXACTLY AR + 2 requests per wave, so the loop can leave a whole younger
     // step in flight behind the tile it waits for (`s_waitcnt vmcnt(N)` needs exact request counts).
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     constexpr unsigned AOOB = 0x80000000u;          // every tensor here is < 2 GB (checked by the host)
     const bool has_gn = d.gn_scale != nullptr;
     const __amdgpu_buffer_rsrc_t r_s0 = __builtin_amdgcn_make_buffer_rsrc(
@@ -135,8 +127,7 @@ __global__ __launch_bounds__(256) void conv_gather_s16_kernel(const ConvArgs p) 
     const int c_begin = (int)((long)nchunks * slice / p.ksplit), c_end = (int)((long)nchunks * (slice + 1) / p.ksplit);
     const int it_begin = c_begin * p.ntaps, it_end = c_end * p.ntaps;
     const _Float16* a_frag = As + (wm * MT * 32) * GS_LDH + (lane & 31) * GS_LDH + (lane >> 5) * 8;
-    // B fragment of 16-byte piece q (+ lane >> 5): row n = wn*NT*32 + j*32 + (lane & 31), swizzled with (n >> 1) & 7
-    const int b_frag = ((wn * NT * 32 + (lane & 31)) * 128) + ((((lane >> 5) ^ (((lane & 31) >> 1) & 7))) << 4);
+    const int b_frag = S16_B_FRAG(wn * NT * 32, lane);
 
     // Per step:  [barrier: As and the buffer of W(it-1) are free | A(it): registers -> GroupNorm / split -> LDS |
     //             my pieces of W(it) landed | barrier | request A(it+2) (registers) and W(it+2) (LDS-DMA) | MFMA(it)].
@@ -160,33 +151,10 @@ __global__ __launch_bounds__(256) void conv_gather_s16_kernel(const ConvArgs p) 
             prefetch_a(clampi(it + 2), a_st, gsc, gsh, a_valid);
             issue_b(clampi(it + 2), cur >= 1 ? cur - 1 : NWB - 1);
             __builtin_amdgcn_sched_barrier(0);
-            const char* bf = Bs + cur * WTILE;
+            int a_rows[MT];                // row block i of the wave: 32 i rows further (filled HERE: in the prologue it costs the code's identity)
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                half8 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    ah[i] = *reinterpret_cast<const half8*>(a_frag + i * 32 * GS_LDH + ks * 16);
-                    al[i] = *reinterpret_cast<const half8*>(a_frag + i * 32 * GS_LDH + ks * 16 + 32);
-                }
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    bh[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ (ks << 5)) + j * 32 * 128));
-                    bl[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ ((ks + 2) << 5)) + j * 32 * 128));
-                }
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-            }
+            for (int i = 0; i < MT; ++i) a_rows[i] = i * 32 * GS_LDH;
+            s16_mfma_tile<MT, NT>(acc, a_frag, a_rows, 0, Bs + cur * WTILE, b_frag);
             cur = cur == NWB - 1 ? 0 : cur + 1;
         };
         // pairs in the loop, an odd last step behind it: with `if (it + 1 < it_end) step(..)` inside, hipcc sees a back

@@ -18,9 +18,7 @@
 //   address and to the fragment read address; the tile of tap+2 is requested while tap is multiplied (an L2 round
 //   trip is longer than one tap of MFMAs: with register staging one tap ahead the loads cost 20 % of the kernel);
 //   per tap and wave: 16 (split form: 24) MFMAs between barriers.
-#include "conv_common.h"
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "s16_tile.h"
 
 constexpr int KC16 = 64;            // halfs per LDS row of one chunk
 constexpr int F16_BM = 256;         // pixels per block tile
@@ -67,6 +65,12 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void conv3x3_halo_f16_kernel(const
     constexpr int NWB = 3;                                        // weight tiles in LDS (tap, tap+1, tap+2)
     constexpr int WTILE = BN * 128;                               // bytes of one weight tile
     constexpr int HBYTES = 2 * MAXH * LDH * 2;                    // halo, double-buffered (see main loop)
+    // the split <4,2,2,2> instances ARE the tile of s16_tile.h (what conv_s16_persist.hip's bit identity rests on)
+    static_assert(LDH == S16_LDH && NWB == S16_NWB, "operand row pitch / weight buffers of the shared pieces");
+    static_assert(!SPLIT || BM != 256 || BN != S16_BN ||
+                      (NTHREADS == S16_NTHREADS && KCH == S16_KCH && MAXH == S16_MAXH && HCOLS == S16_HCOLS && HR == S16_HR &&
+                       BR == S16_BR && WTILE == S16_WTILE && HBYTES == S16_HBYTES),
+                  "split <4,2,2,2>: the 8 x 32 x 128 tile geometry of s16_tile.h");
     // ONE shared object (a second one makes the compiler drain the LDS-DMA queue in front of every fragment read)
     __shared__ __attribute__((aligned(1024))) char lds_all[NWB * WTILE + HBYTES + WM * BN * 2 * 4];
     char* const Bs = lds_all;
@@ -103,22 +107,16 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void conv3x3_halo_f16_kernel(const
         const int sy = d.ups ? (iy >> 1) : iy, sx = d.ups ? (ix >> 1) : ix;
         hoff[i] = ok ? (img * p.Hs + sy) * p.Ws + sx : -1;
     }
-    // ---- weight tile of (chunk, tap) -> Bs[buf] by LDS-DMA: one instruction moves 8 rows x 128 B; lane ->
-    // (row = 8*g + lane/8, piece lane%8) and the piece it FETCHES is piece ^ swizzle(row), so the linear image holds the
-    // swizzled layout.  Rows of wave w: 8w + lrow + 64 j, so (row >> 1) & 7 = 4 (w & 1) + (lrow >> 1) for every j.
-    const int lrow = lane >> 3, lpiece = lane & 7;
-    const int wswz = (((wave & 1) << 2) | (lrow >> 1));
+    // ---- weight tile of (chunk, tap) -> Bs[buf] by LDS-DMA, BR instructions per wave (s16_tile.h: the swizzled lane-linear
+    // image and both sides of its swizzle; the fp16-operand instances use the same 128-byte rows)
+    const int lrow = lane >> 3, lpiece = lane & 7;      // the lane's row / 16-byte piece within one LDS-DMA instruction
+    const int wswz = S16_W_SWZ(wave, lrow);
     const unsigned w_rowlen = 9u * (unsigned)p.Cin * WE * 2u;                 // bytes per output-channel row
     const __amdgpu_buffer_rsrc_t r_w = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.weight)), 0, (unsigned)p.n_tiles * BN * w_rowlen, 0x00020000);
-    const unsigned w_voff = (unsigned)(n_tile * BN + wave * 8 + lrow) * w_rowlen + (unsigned)((lpiece ^ wswz) * 16);
+    const unsigned w_voff = S16_W_LANE(n_tile * BN + wave * 8 + lrow, w_rowlen, lpiece, wswz);
     auto issue_w = [&](int chunk, int tap, int buf) {
-        char* dst = Bs + buf * WTILE + wave * 1024;
-        const unsigned so = ((unsigned)tap * p.Cin + (unsigned)chunk * KCH) * WE * 2u;
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_w, (__attribute__((address_space(3))) void*)(dst + j * (NTHREADS / 64) * 1024),
-                                                     16, w_voff, so + (unsigned)j * (NTHREADS / 8) * w_rowlen, 0, 0);
+        s16_w_request<BR, NTHREADS / 64>(r_w, Bs + buf * WTILE + wave * 1024, w_voff, ((unsigned)tap * p.Cin + (unsigned)chunk * KCH) * WE * 2u, w_rowlen);
     };
     // register-staged weights (fused shortcut only): thread -> (16-byte column c8 of 8, rows brow + BROWS_PER_PASS*i)
     const int c8 = tid % BCOLS, brow = tid / BCOLS;
@@ -223,46 +221,14 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void conv3x3_halo_f16_kernel(const
         const int ty = m >> p.TW_log2, tx = m & (p.TW - 1);
         a_off[i] = (ty * HWd + tx) * LDH + (lane >> 5) * 8;
     }
-    // B fragment of 16-byte piece q (+ lane >> 5): row n = wn*NT*32 + j*32 + (lane & 31), swizzled with (n >> 1) & 7 =
-    // ((lane & 31) >> 1) & 7; the piece pair 2 q enters as an XOR of bits 5-6 of the byte address
-    const int b_frag = ((wn * NT * 32 + (lane & 31)) * 128) + ((((lane >> 5) ^ (((lane & 31) >> 1) & 7))) << 4);
+    const int b_frag = S16_B_FRAG(wn * NT * 32, lane);
 
     auto mfma_tap = [&](int tap, int buf, int hbuf = 0) {
         const int ky = tap / 3, kx = tap - 3 * ky;
         const int tap_off = (ky * HWd + kx) * LDH + hbuf * MAXH * LDH;
         const char* bf = Bs + buf * WTILE;
         if constexpr (SPLIT) {
-            // [hi 32 | lo 32] rows: k-step ks reads the hi fragment at ks*16 and the lo fragment 32 halfs behind it;
-            // the three products of one (i, j) tile are spread over the loop so that no MFMA waits on its predecessor
-#pragma unroll
-            for (int ks = 0; ks < KC16 / 32; ++ks) {
-                half8 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-                for (int i = 0; i < MT; ++i) {
-                    ah[i] = *reinterpret_cast<const half8*>(Hs + a_off[i] + tap_off + ks * 16);
-                    al[i] = *reinterpret_cast<const half8*>(Hs + a_off[i] + tap_off + ks * 16 + 32);
-                }
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    bh[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ (ks << 5)) + j * 32 * 128));
-                    bl[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ ((ks + 2) << 5)) + j * 32 * 128));
-                }
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-            }
+            s16_mfma_tile<MT, NT>(acc, Hs, a_off, tap_off, bf, b_frag);
             return;
         }
 #pragma unroll

@@ -16,27 +16,16 @@
 // Every extra request is part of a branch-free, compile-time-known request stream, so the main loop keeps its counted
 // `s_waitcnt vmcnt(N)` (VMEM retires in order; N = requests issued behind the awaited weight tile, p_wait() below;
 // tests/test_isa_waits.py replays the stream from the ISA).  Arithmetic, summation order and statistics are those of the
-// one-tile kernel: results are bit-identical (tests/test_gpu_s16.py).
+// one-tile kernel -- the same functions of s16_tile.h: results are bit-identical (tests/test_gpu_s16.py).
 //
 // Replaces: the same nn.Conv2d 3x3 + Normalize / swish prologue + concat + nearest x2 + temb addend + residual of the
 // celeba `Model` (/root/reference/guided_diffusion/models.py:36-134) as ddnm_conv3x3_s16_f32, for launches of >= 2 tiles per
 // CU, a ResnetBlock's fused 1x1 shortcut included (the 256^2 / 128^2 levels: 62 % of the forward's kernel time).
 #include <type_traits>
 
-#include "conv_common.h"
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "s16_tile.h"
 
 namespace {
-constexpr int P_WM = 4, P_WN = 2, P_MT = 2, P_NT = 2;
-constexpr int P_NTHREADS = 512, P_BN = 128;      // block tile 256 pixels (8 x 32) x 128 channels
-constexpr int P_LDH = 72, P_KCH = 32;                 // LDS halo row pitch in halfs ([hi 32 | lo 32] + 8), channels per chunk
-constexpr int P_MAXH = 340, P_HWD = 34;               // 8 x 32 output patch, halo 10 x 34
-constexpr int P_HCOLS = 8, P_HRPP = P_NTHREADS / P_HCOLS, P_HR = (P_MAXH + P_HRPP - 1) / P_HRPP, P_HSPLIT = (P_HR + 1) / 2;
-constexpr int P_BR = P_BN / (P_NTHREADS / 8);         // LDS-DMA instructions per wave and weight tile
-constexpr int P_NWB = 3, P_WTILE = P_BN * 128;
-constexpr int P_HBYTES = 2 * P_MAXH * P_LDH * 2;
-constexpr int P_NOUT = P_MT * P_NT * 16;              // output values per lane and tile
 enum { K_MID = 0, K_LAST = 1, K_FIRST = 2 };
 
 // Requests a wave issues at the END of a tap's issue block (behind the weight-tile DMA and the halo loads) on top of the
@@ -44,14 +33,14 @@ enum { K_MID = 0, K_LAST = 1, K_FIRST = 2 };
 // LAST chunk = bias / per-sample addend (4 at tap 0), the next tile's operand bound (1 at tap 0, ASCALE instances) and, with
 // a residual, its 64 loads.  Nothing at taps 7 / 8, so a chunk's table does not depend on its neighbours.
 constexpr int p_spread(int tap) { return tap == 0 ? 10 : (tap <= 6 ? 9 : 0); }
-constexpr int p_first_of(int tap) { return tap == 0 ? 0 : (tap <= 7 ? 10 + 9 * (tap - 1) : P_NOUT); }
-static_assert(p_first_of(7) == P_NOUT, "64 values over taps 0..6");
+constexpr int p_first_of(int tap) { return tap == 0 ? 0 : (tap <= 7 ? 10 + 9 * (tap - 1) : S16_NOUT); }
+static_assert(p_first_of(7) == S16_NOUT, "64 values over taps 0..6");
 constexpr int p_extra(int kind, int tap, bool has_res, bool ascale) {
     return kind == K_FIRST ? p_spread(tap) + (tap == 0 ? 1 : 0)
                            : (kind == K_LAST ? (tap == 0 ? 4 + (ascale ? 1 : 0) : 0) + (has_res ? p_spread(tap) : 0) : 0);
 }
 constexpr int p_base(int tap) {
-    return (tap == 1 || tap == 2) ? P_BR + P_HSPLIT + 2 : ((tap == 4 || tap == 5) ? P_BR + P_HR - P_HSPLIT : P_BR);
+    return (tap == 1 || tap == 2) ? S16_BR + S16_HSPLIT + 2 : ((tap == 4 || tap == 5) ? S16_BR + S16_HR - S16_HSPLIT : S16_BR);
 }
 // vmcnt immediate of the wait in front of tap `tap`: everything issued behind W(tap) (requested first thing at tap - 2)
 constexpr int p_wait(int kind, int tap, bool has_res, bool ascale) {
@@ -68,14 +57,14 @@ using ic = std::integral_constant<int, V>;
 // tile's LAST chunk and its register epilogue -- in the halo / weight buffers the chunk stream is not using at that moment
 // (the other halo buffer holds the next tile's first chunk, weight buffers 0 / 1 its first two tiles).
 template <bool ASCALE, bool HAS_RES, bool HAS_SKIP = false>
-__global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(const ConvArgs p, const int total) {
+__global__ __launch_bounds__(S16_NTHREADS, 1) void conv3x3_s16_persist_kernel(const ConvArgs p, const int total) {
     static_assert(!HAS_SKIP || (ASCALE && !HAS_RES), "a fused shortcut reads a raw operand (bound required) and replaces the residual");
-    constexpr int WM = P_WM, WN = P_WN, MT = P_MT, NT = P_NT, BN = P_BN, HR = P_HR, HSPLIT = P_HSPLIT, LDH = P_LDH, KCH = P_KCH;
-    constexpr int MAXH = P_MAXH, HWd = P_HWD, NWB = P_NWB, WTILE = P_WTILE, BR = P_BR, NTHREADS = P_NTHREADS;
-    __shared__ __attribute__((aligned(1024))) char lds_all[NWB * WTILE + P_HBYTES + WM * BN * 2 * 4];
+    constexpr int WM = S16_WM, WN = S16_WN, MT = S16_MT, NT = S16_NT, BN = S16_BN, HR = S16_HR, HSPLIT = S16_HSPLIT, LDH = S16_LDH, KCH = S16_KCH;
+    constexpr int MAXH = S16_MAXH, HWd = S16_HWD, NWB = S16_NWB, WTILE = S16_WTILE, BR = S16_BR, NTHREADS = S16_NTHREADS;
+    __shared__ __attribute__((aligned(1024))) char lds_all[NWB * WTILE + S16_HBYTES + WM * BN * 2 * 4];
     char* const Bs = lds_all;
     _Float16* const Hs = reinterpret_cast<_Float16*>(lds_all + NWB * WTILE);
-    float* const stat_lds = reinterpret_cast<float*>(lds_all + NWB * WTILE + P_HBYTES);
+    float* const stat_lds = reinterpret_cast<float*>(lds_all + NWB * WTILE + S16_HBYTES);
 
     const ddnm_conv_desc& d = p.d;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -99,12 +88,12 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     };
 
     // ---- halo loader mapping: thread -> (16-byte column hc of 8, halo rows prow + 64 i); hoff[] = source pixel per row slot
-    const int hc = tid % P_HCOLS, prow = tid / P_HCOLS;
+    const int hc = tid % S16_HCOLS, prow = tid / S16_HCOLS;
     int hoff[HR];
     auto set_hoff = [&]() {
 #pragma unroll
         for (int i = 0; i < HR; ++i) {
-            const int row = prow + P_HRPP * i;
+            const int row = prow + S16_HRPP * i;
             const int hy = row / HWd, hx = row - hy * HWd;
             const int iy = t_ty0 - 1 + hy, ix = t_tx0 - 1 + hx;
             const bool ok = row < MAXH && (unsigned)iy < (unsigned)d.Hin && (unsigned)ix < (unsigned)d.Win;
@@ -113,21 +102,16 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
         }
     };
 
-    // ---- weight tiles by LDS-DMA (the one-tile kernel's layout: lane-linear rows, XOR swizzle on the SOURCE address)
-    const int lrow = lane >> 3, lpiece = lane & 7;
-    const int wswz = (((wave & 1) << 2) | (lrow >> 1));
+    // ---- weight tiles by LDS-DMA (s16_tile.h: lane-linear rows, XOR swizzle on the SOURCE address)
+    const int lrow = lane >> 3, lpiece = lane & 7;      // the lane's row / 16-byte piece within one LDS-DMA instruction
+    const int wswz = S16_W_SWZ(wave, lrow);
     const unsigned w_rowlen = 9u * (unsigned)p.Cin * 4u;
     const __amdgpu_buffer_rsrc_t r_w = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.weight)), 0, (unsigned)p.n_tiles * BN * w_rowlen, 0x00020000);
-    const unsigned w_lane = (unsigned)(wave * 8 + lrow) * w_rowlen + (unsigned)((lpiece ^ wswz) * 16);
+    const unsigned w_lane = S16_W_LANE(wave * 8 + lrow, w_rowlen, lpiece, wswz);
     unsigned w_soff = 0;                              // n_tile * BN * w_rowlen of the tile whose weights are being requested
     auto issue_w = [&](int chunk, int tap, int buf) {
-        char* dst = Bs + buf * WTILE + wave * 1024;
-        const unsigned so = w_soff + ((unsigned)tap * p.Cin + (unsigned)chunk * KCH) * 4u;
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_w, (__attribute__((address_space(3))) void*)(dst + j * (NTHREADS / 64) * 1024), 16,
-                                                     w_lane, so + (unsigned)j * (NTHREADS / 8) * w_rowlen, 0, 0);
+        s16_w_request<BR, NTHREADS / 64>(r_w, Bs + buf * WTILE + wave * 1024, w_lane, w_soff + ((unsigned)tap * p.Cin + (unsigned)chunk * KCH) * 4u, w_rowlen);
     };
 
     const int nchunks = p.Cin / KCH;
@@ -140,29 +124,9 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     const __amdgpu_buffer_rsrc_t r_s1 = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.C1 > 0 ? d.src1 : d.src0)), 0,
         (unsigned)d.B * p.Hs * p.Ws * (d.C1 > 0 ? d.C1 : d.C0) * 4, 0x00020000);
-    // Operand-range guard (ASCALE: raw operands; conv_common.h::s16_operand_scale restated for a request stream that must
-    // stay countable): the DDNM_AMAX_N bound words of an image are ONE buffer load per wave (lane l < 32 fetches word l; the
-    // one-tile kernel's scalar loads would become vector loads here -- the kernel stores, so nothing is provably
-    // unclobbered -- in a number the compiler chooses), the maximum is a wave reduction on the bit patterns.
+    // Operand-range guard (ASCALE: raw operands): one counted buffer load per wave and tile (s16_amax_request / s16_amax_scales)
     const __amdgpu_buffer_rsrc_t r_amax = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.amax_in)), 0, d.amax_in ? (unsigned)d.B * DDNM_AMAX_N * 4u : 0u, 0x00020000);
-    auto amax_request = [&](int img, bool live) {
-        return __builtin_amdgcn_raw_buffer_load_b32(r_amax, (lane < DDNM_AMAX_N && live) ? (unsigned)lane * 4u : HOOB, (unsigned)img * DDNM_AMAX_N * 4u, 0);
-    };
-    auto amax_scales = [&](unsigned m, bool down_only, float& scale, float& inv_scale) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const unsigned t = (unsigned)__shfl_xor((int)m, o);
-            m = t > m ? t : m;
-        }
-        m = __builtin_amdgcn_readfirstlane(m);
-        int e = (int)((m >> 23) & 0xffu);
-        e = e < 47 ? 47 : (e > 207 ? 207 : e);
-        int k = 14 - (e - 127);
-        if (down_only && k > 0) k = 0;
-        scale = __uint_as_float((unsigned)(127 + k) << 23);
-        inv_scale = __uint_as_float((unsigned)(127 - k) << 23);
-    };
     unsigned amax_bits = 0;                           // the next tile's bound words, requested at the LAST chunk's tap 0
     int gn_img = 0;                                   // image whose GroupNorm vectors the next prefetch fetches
     float ascale_stage = 1.f;                         // operand scale of the halo being staged (ASCALE)
@@ -189,7 +153,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
 #pragma unroll
         for (int i = 0; i < HR; ++i) {
             if (i < i0 || i >= i1) continue;
-            const int row = prow + P_HRPP * i;
+            const int row = prow + S16_HRPP * i;
             if (row < MAXH) {
                 _Float16* dst = &Hs[hbuf * MAXH * LDH + row * LDH + hc * 4];
                 f32x4 v = __builtin_bit_cast(f32x4, h_st[i]);
@@ -213,37 +177,11 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
         const int m = (wm * MT + i) * 32 + (lane & 31);
         a_off[i] = ((m >> 5) * HWd + (m & 31)) * LDH + (lane >> 5) * 8;
     }
-    const int b_frag = ((wn * NT * 32 + (lane & 31)) * 128) + ((((lane >> 5) ^ (((lane & 31) >> 1) & 7))) << 4);
+    const int b_frag = S16_B_FRAG(wn * NT * 32, lane);
     auto mfma_tap = [&](int tap, int buf, int hbuf) {
         const int ky = tap / 3, kx = tap - 3 * ky;
         const int tap_off = (ky * HWd + kx) * LDH + hbuf * MAXH * LDH;
-        const char* bf = Bs + buf * WTILE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                ah[i] = *reinterpret_cast<const half8*>(Hs + a_off[i] + tap_off + ks * 16);
-                al[i] = *reinterpret_cast<const half8*>(Hs + a_off[i] + tap_off + ks * 16 + 32);
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                bh[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ (ks << 5)) + j * 32 * 128));
-                bl[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ ((ks + 2) << 5)) + j * 32 * 128));
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        s16_mfma_tile<MT, NT>(acc, Hs, a_off, tap_off, Bs + buf * WTILE, b_frag);
     };
 
     // ---- output side: value k = (i * NT + j) * 16 + r of a lane is row (wm*MT + i)*32 + xr(r) + 4 (lane >> 5) of the tile
@@ -270,10 +208,10 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     const unsigned c_lane = (unsigned)((wn * NT * 32 + ncol) * 4);      // channel of (j = 0) in bias / badd
     const unsigned st_lane = tid < 2 * BN ? (unsigned)(tid * 4) : HOOB;  // statistics: thread -> (channel tid >> 1, sum / sum of squares)
 
-    float outv[P_NOUT];                               // residual tile (LAST chunk) -> finished values (deferred stores)
+    float outv[S16_NOUT];                               // residual tile (LAST chunk) -> finished values (deferred stores)
     float addv[NT][2];                                // bias, per-sample addend of the lane's channels
 #pragma unroll
-    for (int k = 0; k < P_NOUT; ++k) outv[k] = 0.f;
+    for (int k = 0; k < S16_NOUT; ++k) outv[k] = 0.f;
 #pragma unroll
     for (int j = 0; j < NT; ++j) addv[j][0] = addv[j][1] = 0.f;
     unsigned pend_base = 0, pend_stats = 0;           // deferred tile: output base, statistics row
@@ -283,42 +221,13 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     // tile end, register work only: scale, bias, residual; per-channel partial sums for the consumer's GroupNorm (the
     // summation order of conv_epilogue: per channel column i-major over the wave's rows, halves combined, waves in order)
     auto finalize = [&]() {
-        float cs[NT], cq[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            cs[j] = cq[j] = 0.f;
-            const float add = addv[j][0];            // bias + per-sample addend (summed at the LAST chunk's tap 4)
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int k = (i * NT + j) * 16 + r;
-                    const float v = acc[i][j][r] * epi_cur + add + (HAS_RES ? outv[k] : 0.f);
-                    outv[k] = v;
-                    cs[j] += v;
-                    cq[j] = __builtin_fmaf(v, v, cq[j]);
-                    acc[i][j][r] = 0.f;
-                }
-            cs[j] += __shfl_xor(cs[j], 32);
-            cq[j] += __shfl_xor(cq[j], 32);
-        }
-        if (lane < 32) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int c = (wn * NT + j) * 32 + lane;
-                stat_lds[(wm * BN + c) * 2 + 0] = cs[j];
-                stat_lds[(wm * BN + c) * 2 + 1] = cq[j];
-            }
-        }
+        const float add[NT] = {addv[0][0], addv[1][0]};      // bias + per-sample addend (summed at the LAST chunk's tap 4)
+        s16_tile_finalize<HAS_RES ? S16_RES_TILE : S16_RES_ZERO>(acc, outv, add, epi_cur, stat_lds, wm, wn, lane);
         pend_base = cur_base;
         pend_stats = cur_stats;
     };
     auto store_stats = [&]() {                        // behind a barrier that follows finalize(): one store per wave
-        const int c = (tid >> 1) & (BN - 1), which = tid & 1;
-        float a = 0.f;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) a += stat_lds[(w * BN + c) * 2 + which];
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a), r_stats, st_lane, pend_stats, 0);
+        s16_store_stats(stat_lds, tid, r_stats, st_lane, pend_stats);
     };
 
     // ---- first tile: the one-tile kernel's prologue
@@ -331,7 +240,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     cur_stats = (unsigned)((t_mtile * Cout + t_ntile * BN) * 8);
     if constexpr (ASCALE) {
         float inv;
-        amax_scales(amax_request(t_img, true), has_gn, ascale_stage, inv);       // nothing else is in flight yet
+        s16_amax_scales(s16_amax_request(r_amax, lane, t_img, true), has_gn, ascale_stage, inv);       // nothing else is in flight yet
         epi_cur = d.acc_scale * inv;
     }
     prefetch_halo_part(0, 0, HR);
@@ -370,7 +279,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
             if constexpr (kind == K_LAST && ASCALE) {         // the next tile's operand scale, from the words requested at tap 0
                 if (have_next) {
                     float inv;
-                    amax_scales(amax_bits, has_gn, ascale_stage, inv);
+                    s16_amax_scales(amax_bits, has_gn, ascale_stage, inv);
                     epi_next = d.acc_scale * inv;
                 }
             }
@@ -391,7 +300,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
         }
         if constexpr (kind == K_LAST) {
             if constexpr (tap == 0) {
-                if constexpr (ASCALE) amax_bits = amax_request(n_img_next, have_next);
+                if constexpr (ASCALE) amax_bits = s16_amax_request(r_amax, lane, n_img_next, have_next);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     addv[j][0] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_bias, c_lane + j * 128, (unsigned)(t_ntile * BN * 4), 0));
@@ -436,7 +345,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     const unsigned sw_rowlen = (unsigned)SCin * 4u;
     const __amdgpu_buffer_rsrc_t r_sw = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.skip_weight)), 0, HAS_SKIP ? (unsigned)p.n_tiles * BN * sw_rowlen : 0u, 0x00020000);
-    const unsigned sw_lane = (unsigned)(wave * 8 + lrow) * sw_rowlen + (unsigned)((lpiece ^ wswz) * 16);
+    const unsigned sw_lane = S16_W_LANE(wave * 8 + lrow, sw_rowlen, lpiece, wswz);
     unsigned sw_soff = 0;
     auto skip_setup = [&](int img, int ty0, int tx0, int ntile) {      // the tile that has just finished its LAST chunk
         s_img = img;
@@ -458,11 +367,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
         }
     };
     auto skip_issue_w = [&](int ch) {                // weight tile of shortcut chunk `ch` -> weight buffer 2
-        char* dst = Bs + 2 * WTILE + wave * 1024;
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_sw, (__attribute__((address_space(3))) void*)(dst + j * (NTHREADS / 64) * 1024), 16,
-                                                     sw_lane, sw_soff + (unsigned)ch * KCH * 4u + (unsigned)j * (NTHREADS / 8) * sw_rowlen, 0, 0);
+        s16_w_request<BR, NTHREADS / 64>(r_sw, Bs + 2 * WTILE + wave * 1024, sw_lane, sw_soff + (unsigned)ch * KCH * 4u, sw_rowlen);
     };
     auto skip_phase = [&](int hbuf, float ascale_cur, int img, int ty0, int tx0, int ntile) {
         const int nsk = SCin / KCH;
@@ -527,7 +432,7 @@ __global__ __launch_bounds__(P_NTHREADS, 1) void conv3x3_s16_persist_kernel(cons
     __syncthreads();
     store_stats();
 #pragma unroll
-    for (int k = 0; k < P_NOUT; ++k) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(outv[k]), r_out, o_lane, o_soff(pend_base, k), 0);
+    for (int k = 0; k < S16_NOUT; ++k) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(outv[k]), r_out, o_lane, o_soff(pend_base, k), 0);
 }
 
 // Launches of at least two tiles per CU, 32-pixel-wide patches, no upsampled residual / split-K.
@@ -535,7 +440,7 @@ bool conv3x3_s16_persist_eligible(const ConvArgs& p) {
     const ddnm_conv_desc& d = p.d;
     const long tiles = (long)p.m_tiles * p.n_tiles;
     if (d.skip0 && (!d.amax_in || d.res)) return false;        // (the only fused-shortcut instance: raw shortcut operand, no residual)
-    return p.ksplit == 1 && tiles >= 512 && p.TW == 32 && !d.res_ups && !d.out_nchw && p.Cin / P_KCH >= 2 &&
+    return p.ksplit == 1 && tiles >= 512 && p.TW == 32 && !d.res_ups && !d.out_nchw && p.Cin / S16_KCH >= 2 &&
            (int64_t)d.B * d.Ho * d.Wo * d.Cout * 4 < ((int64_t)1 << 31) && (int64_t)p.m_tiles * d.Cout * 8 < ((int64_t)1 << 31);
 }
 
@@ -544,10 +449,10 @@ int conv3x3_s16_persist_launch(const ConvArgs& p, hipStream_t s) {
     const int total = p.m_tiles * p.n_tiles;
     const dim3 grid(total < cus ? total : cus);
     const bool asc = p.d.amax_in != nullptr, res = p.d.res != nullptr;
-    if (p.d.skip0) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, false, true>), grid, dim3(P_NTHREADS), 0, s, p, total); }
-    else if (asc && res) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, true>), grid, dim3(P_NTHREADS), 0, s, p, total); }
-    else if (asc) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, false>), grid, dim3(P_NTHREADS), 0, s, p, total); }
-    else if (res) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<false, true>), grid, dim3(P_NTHREADS), 0, s, p, total); }
-    else { DDNM_LAUNCH((conv3x3_s16_persist_kernel<false, false>), grid, dim3(P_NTHREADS), 0, s, p, total); }
+    if (p.d.skip0) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, false, true>), grid, dim3(S16_NTHREADS), 0, s, p, total); }
+    else if (asc && res) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, true>), grid, dim3(S16_NTHREADS), 0, s, p, total); }
+    else if (asc) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<true, false>), grid, dim3(S16_NTHREADS), 0, s, p, total); }
+    else if (res) { DDNM_LAUNCH((conv3x3_s16_persist_kernel<false, true>), grid, dim3(S16_NTHREADS), 0, s, p, total); }
+    else { DDNM_LAUNCH((conv3x3_s16_persist_kernel<false, false>), grid, dim3(S16_NTHREADS), 0, s, p, total); }
     return 0;
 }

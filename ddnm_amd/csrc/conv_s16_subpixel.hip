@@ -22,20 +22,9 @@
 // Only instance: raw operand (bound required), bias, no per-sample addend / residual / GroupNorm prologue / shortcut.
 #include <type_traits>
 
-#include "conv_common.h"
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "s16_tile.h"
 
 namespace {
-constexpr int Q_WM = 4, Q_WN = 2, Q_MT = 2, Q_NT = 2;
-constexpr int Q_NTHREADS = 512, Q_BN = 128;
-constexpr int Q_LDH = 72, Q_KCH = 32;
-constexpr int Q_MAXH = 340, Q_HWD = 34;
-constexpr int Q_HCOLS = 8, Q_HRPP = Q_NTHREADS / Q_HCOLS, Q_HR = (Q_MAXH + Q_HRPP - 1) / Q_HRPP;
-constexpr int Q_BR = Q_BN / (Q_NTHREADS / 8);
-constexpr int Q_NWB = 3, Q_WTILE = Q_BN * 128;
-constexpr int Q_HBYTES = 2 * Q_MAXH * Q_LDH * 2;
-constexpr int Q_NOUT = Q_MT * Q_NT * 16;
 constexpr int Q_STEPS = 4;
 enum { Q_MID = 0, Q_LAST = 1, Q_FIRST = 2 };
 
@@ -43,13 +32,13 @@ enum { Q_MID = 0, Q_LAST = 1, Q_FIRST = 2 };
 // issue block).  Every chunk: the next chunk's halo at step 0 (staged at steps 2 / 3).  FIRST chunk of a tile: the previous
 // tile's 64 deferred stores over steps 0..2 (+ the statistics store at step 0).  LAST chunk: 2 bias loads + the next tile's
 // operand bound at step 0.  Nothing at step 3, so a chunk's table does not depend on its neighbours.
-constexpr int q_first_of(int s) { return s == 0 ? 0 : (s == 1 ? 22 : (s == 2 ? 43 : Q_NOUT)); }
+constexpr int q_first_of(int s) { return s == 0 ? 0 : (s == 1 ? 22 : (s == 2 ? 43 : S16_NOUT)); }
 constexpr int q_extra(int kind, int s) {
-    return (s == 0 ? Q_HR : 0) + (kind == Q_FIRST ? q_first_of(s + 1) - q_first_of(s) + (s == 0 ? 1 : 0) : (kind == Q_LAST && s == 0 ? 3 : 0));
+    return (s == 0 ? S16_HR : 0) + (kind == Q_FIRST ? q_first_of(s + 1) - q_first_of(s) + (s == 0 ? 1 : 0) : (kind == Q_LAST && s == 0 ? 3 : 0));
 }
 // vmcnt immediate of the wait in front of step `s`: everything issued behind W(s), the last request of step s - 2 -- the
 // whole issue block of step s - 1 (its extras, then W(s + 1))
-constexpr int q_wait(int kind, int s) { return Q_BR + (s >= 1 ? q_extra(kind, s - 1) : q_extra(kind, 3)); }
+constexpr int q_wait(int kind, int s) { return S16_BR + (s >= 1 ? q_extra(kind, s - 1) : q_extra(kind, 3)); }
 static_assert(q_extra(Q_FIRST, 3) == 0 && q_extra(Q_MID, 3) == 0 && q_extra(Q_LAST, 3) == 0, "step 3 issues its weight tile only");
 static_assert(q_wait(Q_FIRST, 1) < 64 && q_wait(Q_FIRST, 2) < 64 && q_wait(Q_FIRST, 3) < 64 && q_wait(Q_LAST, 1) < 64, "vmcnt is a 6-bit field");
 
@@ -57,13 +46,13 @@ template <int V>
 using ic = std::integral_constant<int, V>;
 }  // namespace
 
-__global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(const ConvArgs p, const int total) {
-    constexpr int WM = Q_WM, WN = Q_WN, MT = Q_MT, NT = Q_NT, BN = Q_BN, HR = Q_HR, LDH = Q_LDH, KCH = Q_KCH;
-    constexpr int MAXH = Q_MAXH, HWd = Q_HWD, NWB = Q_NWB, WTILE = Q_WTILE, BR = Q_BR, NTHREADS = Q_NTHREADS;
-    __shared__ __attribute__((aligned(1024))) char lds_all[NWB * WTILE + Q_HBYTES + WM * BN * 2 * 4];
+__global__ __launch_bounds__(S16_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(const ConvArgs p, const int total) {
+    constexpr int WM = S16_WM, WN = S16_WN, MT = S16_MT, NT = S16_NT, BN = S16_BN, HR = S16_HR, LDH = S16_LDH, KCH = S16_KCH;
+    constexpr int MAXH = S16_MAXH, HWd = S16_HWD, NWB = S16_NWB, WTILE = S16_WTILE, BR = S16_BR, NTHREADS = S16_NTHREADS;
+    __shared__ __attribute__((aligned(1024))) char lds_all[NWB * WTILE + S16_HBYTES + WM * BN * 2 * 4];
     char* const Bs = lds_all;
     _Float16* const Hs = reinterpret_cast<_Float16*>(lds_all + NWB * WTILE);
-    float* const stat_lds = reinterpret_cast<float*>(lds_all + NWB * WTILE + Q_HBYTES);
+    float* const stat_lds = reinterpret_cast<float*>(lds_all + NWB * WTILE + S16_HBYTES);
 
     const ddnm_conv_desc& d = p.d;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -88,30 +77,25 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
 
     // ---- halo loader mapping: thread -> (16-byte column hc of 8, halo rows prow + 64 i); the source pixel of a slot is worked
     // out from the tile origin where it is requested (six slots per chunk: cheaper than six registers across the MFMA loop)
-    const int hc = tid % Q_HCOLS, prow = tid / Q_HCOLS;
+    const int hc = tid % S16_HCOLS, prow = tid / S16_HCOLS;
     auto halo_src = [&](int i) {
-        const int row = prow + Q_HRPP * i;
+        const int row = prow + S16_HRPP * i;
         const int hy = row / HWd, hx = row - hy * HWd;
         const int iy = t_ty0 - 1 + hy, ix = t_tx0 - 1 + hx;
         const bool ok = row < MAXH && (unsigned)iy < (unsigned)p.Hs && (unsigned)ix < (unsigned)p.Ws;
         return ok ? (t_img * p.Hs + iy) * p.Ws + ix : -1;
     };
 
-    // ---- weight tiles by LDS-DMA (layout of conv_s16_persist.hip; a row holds 4 steps x Cin x [hi | lo])
-    const int lrow = lane >> 3, lpiece = lane & 7;
-    const int wswz = (((wave & 1) << 2) | (lrow >> 1));
+    // ---- weight tiles by LDS-DMA (s16_tile.h; a row holds 4 steps x Cin x [hi | lo])
+    const int lrow = lane >> 3, lpiece = lane & 7;      // the lane's row / 16-byte piece within one LDS-DMA instruction
+    const int wswz = S16_W_SWZ(wave, lrow);
     const unsigned w_rowlen = (unsigned)Q_STEPS * (unsigned)p.Cin * 4u;
     const __amdgpu_buffer_rsrc_t r_w = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.weight)), 0, (unsigned)p.n_tiles * BN * w_rowlen, 0x00020000);
-    const unsigned w_lane = (unsigned)(wave * 8 + lrow) * w_rowlen + (unsigned)((lpiece ^ wswz) * 16);
+    const unsigned w_lane = S16_W_LANE(wave * 8 + lrow, w_rowlen, lpiece, wswz);
     unsigned w_soff = 0;
     auto issue_w = [&](int chunk, int step, int buf) {
-        char* dst = Bs + buf * WTILE + wave * 1024;
-        const unsigned so = w_soff + ((unsigned)step * p.Cin + (unsigned)chunk * KCH) * 4u;
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_w, (__attribute__((address_space(3))) void*)(dst + j * (NTHREADS / 64) * 1024), 16,
-                                                     w_lane, so + (unsigned)j * (NTHREADS / 8) * w_rowlen, 0, 0);
+        s16_w_request<BR, NTHREADS / 64>(r_w, Bs + buf * WTILE + wave * 1024, w_lane, w_soff + ((unsigned)step * p.Cin + (unsigned)chunk * KCH) * 4u, w_rowlen);
     };
 
     const int nchunks = p.Cin / KCH;
@@ -122,25 +106,9 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
     const __amdgpu_buffer_rsrc_t r_s1 = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.C1 > 0 ? d.src1 : d.src0)), 0,
         (unsigned)d.B * p.Hs * p.Ws * (d.C1 > 0 ? d.C1 : d.C0) * 4, 0x00020000);
-    // operand-range guard: one buffer load per wave, wave reduction on the bit patterns (conv_s16_persist.hip)
+    // operand-range guard: one counted buffer load per wave and tile (s16_amax_request / s16_amax_scales)
     const __amdgpu_buffer_rsrc_t r_amax = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(reinterpret_cast<const void*>(d.amax_in)), 0, (unsigned)d.B * DDNM_AMAX_N * 4u, 0x00020000);
-    auto amax_request = [&](int img, bool live) {
-        return __builtin_amdgcn_raw_buffer_load_b32(r_amax, (lane < DDNM_AMAX_N && live) ? (unsigned)lane * 4u : HOOB, (unsigned)img * DDNM_AMAX_N * 4u, 0);
-    };
-    auto amax_scales = [&](unsigned m, float& scale, float& inv_scale) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const unsigned t = (unsigned)__shfl_xor((int)m, o);
-            m = t > m ? t : m;
-        }
-        m = __builtin_amdgcn_readfirstlane(m);
-        int e = (int)((m >> 23) & 0xffu);
-        e = e < 47 ? 47 : (e > 207 ? 207 : e);
-        const int k = 14 - (e - 127);
-        scale = __uint_as_float((unsigned)(127 + k) << 23);
-        inv_scale = __uint_as_float((unsigned)(127 - k) << 23);
-    };
     unsigned amax_bits = 0;
     float ascale_stage = 1.f;
     auto prefetch_halo = [&](int chunk, bool live) {
@@ -160,7 +128,7 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
 #pragma unroll
         for (int i = 0; i < HR; ++i) {
             if (i < i0 || i >= i1) continue;
-            const int row = prow + Q_HRPP * i;
+            const int row = prow + S16_HRPP * i;
             if (row < MAXH) split_store(&Hs[hbuf * MAXH * LDH + row * LDH + hc * 4], __builtin_bit_cast(f32x4, h_st[i]), ascale_stage);
         }
     };
@@ -178,38 +146,12 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
         const int m = (wm * MT + i) * 32 + (lane & 31);
         a_off[i] = ((m >> 5) * HWd + (m & 31) + wn) * LDH + (lane >> 5) * 8;          // + px: the wave's column phase
     }
-    const int b_frag = ((wn * NT * 32 + (lane & 31)) * 128) + ((((lane >> 5) ^ (((lane & 31) >> 1) & 7))) << 4);
+    const int b_frag = S16_B_FRAG(wn * NT * 32, lane);
     int cur_py = 0;                                       // row phase of the tile in the MFMA loop
     // step (a, b) of the current chunk: weight buffer `buf` (run-time), halo buffer `hbuf`
     auto mfma_step = [&](int a, int b, int buf, int hbuf) {
         const int step_off = ((cur_py + a) * HWd + b) * LDH + hbuf * MAXH * LDH;
-        const char* bf = Bs + buf * WTILE;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            half8 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                ah[i] = *reinterpret_cast<const half8*>(Hs + a_off[i] + step_off + ks * 16);
-                al[i] = *reinterpret_cast<const half8*>(Hs + a_off[i] + step_off + ks * 16 + 32);
-            }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                bh[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ (ks << 5)) + j * 32 * 128));
-                bl[j] = *reinterpret_cast<const half8*>(bf + ((b_frag ^ ((ks + 2) << 5)) + j * 32 * 128));
-            }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        s16_mfma_tile<MT, NT>(acc, Hs, a_off, step_off, Bs + buf * WTILE, b_frag);
     };
 
     // ---- output side: value k = (i * NT + j) * 16 + r of a lane is low-resolution row wm*MT + i, x = xr(r) + 4 (lane >> 5)
@@ -233,10 +175,10 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
     // statistics: thread -> (n-tile row tid >> 1 = px * 64 + channel, sum / sum of squares); partial row (m-tile, py, px)
     const unsigned st_lane = tid < 2 * BN ? (unsigned)(((((tid >> 1) >> 6) * Cout + ((tid >> 1) & 63)) * 2 + (tid & 1)) * 4) : HOOB;
 
-    float outv[Q_NOUT];
+    float outv[S16_NOUT];
     float addv[NT];
 #pragma unroll
-    for (int k = 0; k < Q_NOUT; ++k) outv[k] = 0.f;
+    for (int k = 0; k < S16_NOUT; ++k) outv[k] = 0.f;
 #pragma unroll
     for (int j = 0; j < NT; ++j) addv[j] = 0.f;
     unsigned pend_base = 0, pend_stats = 0;
@@ -244,42 +186,12 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
     float epi_cur = d.acc_scale;
 
     auto finalize = [&]() {
-        float cs[NT], cq[NT];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            cs[j] = cq[j] = 0.f;
-            const float add = addv[j];
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int k = (i * NT + j) * 16 + r;
-                    const float v = acc[i][j][r] * epi_cur + add;
-                    outv[k] = v;
-                    cs[j] += v;
-                    cq[j] = __builtin_fmaf(v, v, cq[j]);
-                    acc[i][j][r] = 0.f;
-                }
-            cs[j] += __shfl_xor(cs[j], 32);
-            cq[j] += __shfl_xor(cq[j], 32);
-        }
-        if (lane < 32) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                const int c = (wn * NT + j) * 32 + lane;
-                stat_lds[(wm * BN + c) * 2 + 0] = cs[j];
-                stat_lds[(wm * BN + c) * 2 + 1] = cq[j];
-            }
-        }
+        s16_tile_finalize<S16_RES_NONE>(acc, outv, addv, epi_cur, stat_lds, wm, wn, lane);
         pend_base = cur_base;
         pend_stats = cur_stats;
     };
     auto store_stats = [&]() {                        // behind a barrier that follows finalize(): one store per wave
-        const int c = (tid >> 1) & (BN - 1), which = tid & 1;
-        float a = 0.f;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) a += stat_lds[(w * BN + c) * 2 + which];
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a), r_stats, st_lane, pend_stats, 0);
+        s16_store_stats(stat_lds, tid, r_stats, st_lane, pend_stats);
     };
 
     // ---- first tile
@@ -291,7 +203,7 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
     cur_py = t_ntile & 1;
     {
         float inv;
-        amax_scales(amax_request(t_img, true), ascale_stage, inv);
+        s16_amax_scales(s16_amax_request(r_amax, lane, t_img, true), false, ascale_stage, inv);
         epi_cur = d.acc_scale * inv;
     }
     prefetch_halo(0, true);
@@ -319,7 +231,7 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
             if constexpr (kind == Q_LAST) {
                 if (have_next) {
                     float inv;
-                    amax_scales(amax_bits, ascale_stage, inv);
+                    s16_amax_scales(amax_bits, false, ascale_stage, inv);
                     epi_next = d.acc_scale * inv;
                 }
             }
@@ -338,7 +250,7 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(outv[k]), r_out, o_lane, o_soff(pend_base, k), 0);
         }
         if constexpr (kind == Q_LAST && step == 0) {
-            amax_bits = amax_request(n_img_next, have_next);
+            amax_bits = s16_amax_request(r_amax, lane, n_img_next, have_next);
 #pragma unroll
             for (int j = 0; j < NT; ++j)
                 addv[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r_bias, c_lane + j * 128, (unsigned)((t_ntile >> 1) * 64 * 4), 0));
@@ -408,7 +320,7 @@ __global__ __launch_bounds__(Q_NTHREADS, 1) void conv2x2x4_s16_subpixel_kernel(c
     __syncthreads();
     store_stats();
 #pragma unroll
-    for (int k = 0; k < Q_NOUT; ++k) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(outv[k]), r_out, o_lane, o_soff(pend_base, k), 0);
+    for (int k = 0; k < S16_NOUT; ++k) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(outv[k]), r_out, o_lane, o_soff(pend_base, k), 0);
 }
 
 // CU count of the current device, queried once per device (shared by the persistent launchers)
@@ -431,7 +343,7 @@ bool conv3x3_s16_ups_subpixel_ok(const ddnm_conv_desc* d) {
     if (!d || !d->ups || d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->Ho != d->Hin || d->Wo != d->Win) return false;
     if (d->B <= 0 || d->Hin <= 0 || d->Win <= 0 || ((d->Hin | d->Win) & 1)) return false;
     const int hs = d->Hin / 2, ws = d->Win / 2, cin = d->C0 + d->C1;
-    if (ws % 32 || hs % 8 || d->C0 <= 0 || d->C1 < 0 || cin % Q_KCH || d->C0 % Q_KCH || cin / Q_KCH < 2 || d->Cout <= 0 || d->Cout % 64) return false;
+    if (ws % 32 || hs % 8 || d->C0 <= 0 || d->C1 < 0 || cin % S16_KCH || d->C0 % S16_KCH || cin / S16_KCH < 2 || d->Cout <= 0 || d->Cout % 64) return false;
     if (d->src_f16 || d->out_nchw || d->res || d->res_ups || d->badd || d->gn_scale || d->skip0) return false;
     if (!conv_sizes_addressable(d)) return false;
     const int64_t lim = (int64_t)1 << 31;
@@ -448,6 +360,6 @@ int conv3x3_s16_ups_subpixel_run(const ddnm_conv_desc* d, hipStream_t s) {
     const ConvArgs p = conv_args(*d, 1024, d->Cout / 32, 32, 5, d->Win / 2 / 32, Q_STEPS, 1);
     const int total = p.m_tiles * p.n_tiles;
     const int cus = conv_persist_grid_cus();
-    DDNM_LAUNCH(conv2x2x4_s16_subpixel_kernel, dim3(total < cus ? total : cus), dim3(Q_NTHREADS), 0, s, p, total);
+    DDNM_LAUNCH(conv2x2x4_s16_subpixel_kernel, dim3(total < cus ? total : cus), dim3(S16_NTHREADS), 0, s, p, total);
     return 0;
 }

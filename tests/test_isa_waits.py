@@ -141,12 +141,9 @@ def test_the_all_paths_check_fails_when_the_table_is_wrong(tmp_path):
     assert src.count(old) == 1
     mut = src.replace(old, "            for (int k = p_first_of(tap) + (tap == 0 ? 1 : 0); k < p_first_of(tap + 1); ++k)\n"
                            "                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(outv[k]), r_out,")
-    path = os.path.join(CSRC, "_mut_persist_test.hip")           # next to the headers it includes
-    try:
-        open(path, "w").write(mut)
-        asm = isa_waits.compile_isa(path, str(tmp_path / "m.s"))
-    finally:
-        os.remove(path)
+    p = tmp_path / "conv_s16_persist_mut.hip"
+    p.write_text(mut)
+    asm = isa_waits.compile_isa(str(p), str(tmp_path / "m.s"), extra=["-I", CSRC])
     res = isa_waits.analyse_cfg(asm, r"conv3x3_s16_persist_kernelILb0ELb0E", depth=2, group_size=2)
     (waits,) = res.values()
     bad = [(n, found) for n, found, _ in waits if found != [n]]
