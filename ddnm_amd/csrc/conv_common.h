@@ -38,6 +38,10 @@ int conv3x3_s16_persist_launch(const ConvArgs& p, hipStream_t s);
 // sub-pixel form of `nearest x2 -> 3x3` on phase-packed weights (conv_s16_subpixel.hip; ddnm_conv_desc::flags & DDNM_CONV_UPS_SUBPIXEL)
 bool conv3x3_s16_ups_subpixel_ok(const ddnm_conv_desc* d);
 int conv3x3_s16_ups_subpixel_run(const ddnm_conv_desc* d, hipStream_t s);
+// GEMM form of the 1x1 / stride-1 launches of ddnm_conv_gather_s16_f32 (conv1x1_s16.hip), dispatched from conv_gather_s16.hip;
+// `plan_ksplit`, `plan_bm`: split and M tile of the gather plan (they fix the statistics layout the caller sized)
+bool conv1x1_s16_routes(const ddnm_conv_desc* d, int plan_ksplit, int plan_bm);
+int conv1x1_s16_launch(const ddnm_conv_desc* d, int plan_ksplit, int plan_bm, int run_ksplit, hipStream_t s);
 // workgroups of a persistent launch: the CU count of the current device rounded down to a multiple of 8, queried once per device
 int conv_persist_grid_cus();
 

@@ -222,6 +222,12 @@ extern "C" int ddnm_conv_gather_s16_stats_tiles(const ddnm_conv_desc* d) {
     return conv_stats_tiles(d, pl.ksplit, pl.BM);
 }
 
+extern "C" int ddnm_conv_gather_s16_gemm1x1(const ddnm_conv_desc* d) {
+    PlanGS pl;
+    if (!d || !plan_gs(d, &pl)) return DDNM_E_SHAPE;
+    return !(d->flags & DDNM_CONV_ONE_TILE) && conv1x1_s16_routes(d, pl.ksplit, pl.BM) ? 1 : 0;
+}
+
 extern "C" int ddnm_conv_gather_s16_f32(const ddnm_conv_desc* d, void* stream) {
     if (int e = conv_check_desc(d)) return e;
     if (!(d->acc_scale > 0.f)) return DDNM_E_BADARG;
@@ -229,7 +235,12 @@ extern "C" int ddnm_conv_gather_s16_f32(const ddnm_conv_desc* d, void* stream) {
     if (int e = conv_check_gn_ups(d)) return e;
     PlanGS pl;
     if (!plan_gs(d, &pl)) return DDNM_E_SHAPE;
+    const int plan_ksplit = pl.ksplit;
     if ((pl.ksplit = conv_run_ksplit(d, pl.ksplit)) < 0) return pl.ksplit;
+    // 1x1 launches in the GEMM form (conv1x1_s16.hip: one workgroup owns all of K, no slabs, no reduction launch) where
+    // conv1x1_s16_routes says so; DDNM_CONV_ONE_TILE keeps the gather kernel below (A/B timing, comparison partner)
+    if (!(d->flags & DDNM_CONV_ONE_TILE) && conv1x1_s16_routes(d, plan_ksplit, pl.BM))
+        return conv1x1_s16_launch(d, plan_ksplit, pl.BM, pl.ksplit, (hipStream_t)stream);
     // tiles_x = 0: flat strips of BM consecutive pixels of one image
     const ConvArgs p = conv_args(*d, pl.BM, d->Cout / pl.BN, 32, 5, 0, d->ksize * d->ksize, pl.ksplit);
     const dim3 grid(p.m_tiles * p.n_tiles, pl.ksplit);

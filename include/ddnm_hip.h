@@ -93,7 +93,10 @@ typedef struct ddnm_conv_desc {
     int32_t flags;          /* bit 0 (DDNM_CONV_ONE_TILE): ddnm_conv3x3_s16_f32 runs the one-tile-per-workgroup kernel even where
                                the persistent form (>= 2 tiles per CU) applies -- same results bit for bit; for A/B timing
                                bit 1 (DDNM_CONV_UPS_SUBPIXEL): ddnm_conv3x3_s16_f32 with ups = 1 takes `weight` as the PHASE
-                               packing of the upsample convolution (see ddnm_conv3x3_s16_ups_subpixel_supported) */
+                               packing of the upsample convolution (see ddnm_conv3x3_s16_ups_subpixel_supported)
+                               ddnm_conv_gather_s16_f32: bit 0 keeps a 1x1 launch on the gather kernel, bit 2 (DDNM_CONV_GEMM1X1)
+                               sends it to the GEMM form wherever that kernel has a form for it, also where the measured
+                               routing rule would not (see ddnm_conv_gather_s16_gemm1x1); bit 0 wins; for A/B timing */
     /* ABI 5 -- operand-range guard of the split forms (ddnm_conv3x3_s16_f32, ddnm_conv_gather_s16_f32; ignored by every
      * other entry point).  fp16 carries |v| < 65504 only, fp32 -- the arithmetic the reference runs -- does not care, so
      * operands the kernel reads RAW (no GroupNorm in front: src0 / src1 when gn_scale is NULL, skip0 / skip1 always) are
@@ -110,6 +113,7 @@ typedef struct ddnm_conv_desc {
 
 #define DDNM_CONV_ONE_TILE 1
 #define DDNM_CONV_UPS_SUBPIXEL 2
+#define DDNM_CONV_GEMM1X1 4
 #define DDNM_AMAX_N 32   /* bound words per image (= the GroupNorm group count of both networks) */
 
 int ddnm_conv2d_f32(const ddnm_conv_desc* d, void* stream);
@@ -181,6 +185,15 @@ int ddnm_conv_gather_s16_f32(const ddnm_conv_desc* d, void* stream);
 int ddnm_conv_gather_s16_supported(const ddnm_conv_desc* d);
 int64_t ddnm_conv_gather_s16_workspace_floats(const ddnm_conv_desc* d);
 int ddnm_conv_gather_s16_stats_tiles(const ddnm_conv_desc* d);
+/* GEMM form of the 1x1 / stride-1 launches (csrc/conv1x1_s16.hip; addition within ABI 7): 64 x 64 tiles, one workgroup owns
+ * all of K (Cin <= 1024), so the launch writes no split-K slabs and needs no reduction launch; same operands, arithmetic,
+ * workspace and statistics answers as above (a launch the plan splits fills the reduction pass's 4-pixel statistics tiles),
+ * same results bit for bit (it adds in the gather route's order, slice by slice where that route splits K).
+ * Routed where it was measured at most 0.8 x the gather route (profiles/conv1x1_s16_ab.md): Cin <= 512.
+ * 1 when ddnm_conv_gather_s16_f32 runs this descriptor in that form (`stats_out` and `flags` count: set them as the launch
+ * will), 0 when it runs the gather kernel -- always with flags & DDNM_CONV_ONE_TILE --, negative when the family refuses the
+ * shape. */
+int ddnm_conv_gather_s16_gemm1x1(const ddnm_conv_desc* d);
 
 /* 1x1 convolution with fp16 MFMA operands, fp32 accumulate / output: the attention blocks' qkv and proj_out
  * Conv1d(k=1) and un-fused 1x1 shortcuts of the `use_fp16` torso (guided_diffusion/unet.py:222,283-289,301-308).
