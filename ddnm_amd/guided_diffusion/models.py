@@ -28,7 +28,7 @@ Layer order restates models.py:301-341 (forward), :115-134 (ResnetBlock),
 """
 import math
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -55,6 +55,25 @@ class _ResBlock:
 class _Attn:
     def __init__(self, name, c):
         self.name, self.c = name, c
+
+
+# a Downsample / Upsample convolution (c -> c channels) of level `lvl`
+_Resample = namedtuple("_Resample", "name lvl c up")
+# One launch that can run split-fp16 (Model._plan_s16 lists them; the loader packs from the list, the two guards judge it):
+#   name      what `s16_dropped` reports
+#   weights   the checkpoint convolutions that share its accumulator, and with it ONE ops.s16_weight_scale
+#   packs     the `w` keys that hold those weights split: its own pack `<name>.s16` first
+#   norm      (name, resolution, channels) of the GroupNorm that feeds it, or None (a raw operand is scaled per launch)
+#   subpixel  an upsample convolution that also gets the phase packing `<name>.s16_subpixel` (csrc/conv_s16_subpixel.hip)
+_S16Launch = namedtuple("_S16Launch", "name weights packs norm subpixel")
+
+
+def _gn_bound(sd, norm, res, channels):
+    """sqrt(n) * max|gamma| + max|beta| of GroupNorm `norm` (32 groups) over [res, res, channels]: the static bound of its
+    output (Model._guard_normalised_operands), from the host tensors of `sd`."""
+    g = sd[norm + ".weight"].detach().abs().max().item()
+    b = sd[norm + ".bias"].detach().abs().max().item()
+    return math.sqrt(res * res * max(1, channels // 32)) * g + b
 
 
 class Model(_net.GraphedNet):
@@ -88,6 +107,8 @@ class Model(_net.GraphedNet):
         res = self.resolution
         self.down = []
         self.res_blocks = []          # execution order (defines the temb_proj concat layout)
+        self.attns, self.resample = [], []        # all attention blocks / resampling convolutions: down, mid, up as stored
+        self.layers = []              # every block and resampling convolution in state-dict (module registration) order
         block_in = None
         chans = [ch]
         for lvl in range(self.num_resolutions):
@@ -104,17 +125,24 @@ class Model(_net.GraphedNet):
                     attns.append(_Attn(f"down.{lvl}.attn.{ib}", block_in))
                     attns[-1].res = res
                 chans.append(block_in)
+            level = blocks + attns
             has_down = lvl != self.num_resolutions - 1
             if has_down:
                 res //= 2
                 chans.append(block_in)
+                level.append(_Resample(f"down.{lvl}.downsample.conv", lvl, block_in, False))
+                self.resample.append(level[-1])
             self.down.append((blocks, attns, has_down, block_in))
+            self.attns += attns
+            self.layers += level
         self.mid = [_ResBlock("mid.block_1", block_in, block_in), _Attn("mid.attn_1", block_in),
                     _ResBlock("mid.block_2", block_in, block_in)]
         for m in self.mid:
             m.res = res
         self.res_blocks += [self.mid[0], self.mid[2]]
-        self.up = {}
+        self.attns.append(self.mid[1])
+        self.layers += self.mid
+        self.up, up_layers = {}, []
         for lvl in reversed(range(self.num_resolutions)):
             block_out = ch * mult[lvl]
             blocks, attns = [], []
@@ -129,10 +157,16 @@ class Model(_net.GraphedNet):
                 if res in self.attn_resolutions:
                     attns.append(_Attn(f"up.{lvl}.attn.{ib}", block_in))
                     attns[-1].res = res
+            level = blocks + attns
             has_up = lvl != 0
             if has_up:
                 res *= 2
+                level.append(_Resample(f"up.{lvl}.upsample.conv", lvl, block_in, True))
+                self.resample.append(level[-1])
             self.up[lvl] = (blocks, attns, has_up, block_in)
+            self.attns += attns
+            up_layers = level + up_layers          # built from the bottom, registered by level index
+        self.layers += up_layers
         self.final_ch = block_in
         off = 0
         for rb in self.res_blocks:
@@ -140,6 +174,29 @@ class Model(_net.GraphedNet):
             off += rb.cout
         self.temb_total = off
         self.max_ch = max(rb.cin for rb in self.res_blocks)
+        self._plan_s16()
+
+    def _plan_s16(self):
+        """`s16_launches[layer name]`: the launches of that layer that can run split-fp16 (`_S16Launch` above), the layers in the
+        order res_blocks, attns, resample -- the order of `s16_dropped`.  Built from the plan alone."""
+        def launch(name, *fused, norm=None, subpixel=False):
+            weights = (name,) + fused
+            packs = tuple(k + ".s16" for k in weights) + ((name + ".s16_subpixel",) if subpixel else ())
+            return _S16Launch(name, weights, packs, norm, subpixel)
+        t = self.s16_launches = {}
+        for rb in self.res_blocks:
+            n = rb.name
+            # conv2 and its fused shortcut share an accumulator, hence one scale and one verdict on their weight range; the
+            # un-fused form of the shortcut (8 x 8 level: gather kernel) is a launch of its own, with its own scale
+            sc = (n + ".nin_shortcut",) if rb.cin != rb.cout else ()
+            t[n] = [launch(n + ".conv1", norm=(n + ".norm1", rb.res, rb.cin)),
+                    launch(n + ".conv2", *sc, norm=(n + ".norm2", rb.res, rb.cout))] + [launch(k) for k in sc]
+        for a in self.attns:
+            # (`<attn>.qkv`: the q, k, v concatenation -- one launch, one scale)
+            t[a.name] = [launch(a.name + ".qkv", norm=(a.name + ".norm", a.res, a.c)), launch(a.name + ".proj_out")]
+        for cv in self.resample:
+            # sub-pixel form at the level's own (low) resolution: 8 x 32 tiles, 64-channel blocks
+            t[cv.name] = [launch(cv.name, subpixel=cv.up and cv.c % 64 == 0 and (self.resolution >> cv.lvl) % 32 == 0)]
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def state_dict_shapes(self):
@@ -171,22 +228,13 @@ class Model(_net.GraphedNet):
         s["temb.dense.0.weight"], s["temb.dense.0.bias"] = (self.temb_ch, self.ch), (self.temb_ch,)
         s["temb.dense.1.weight"], s["temb.dense.1.bias"] = (self.temb_ch, self.temb_ch), (self.temb_ch,)
         conv("conv_in", self.ch, self.in_channels, 3)
-        for lvl, (blocks, attns, has_down, c) in enumerate(self.down):
-            for rb in blocks:
-                resblock(rb)
-            for a in attns:
-                attn(a)
-            if has_down:
-                conv(f"down.{lvl}.downsample.conv", c, c, 3)
-        resblock(self.mid[0]), attn(self.mid[1]), resblock(self.mid[2])
-        for lvl in range(self.num_resolutions):
-            blocks, attns, has_up, c = self.up[lvl]
-            for rb in blocks:
-                resblock(rb)
-            for a in attns:
-                attn(a)
-            if has_up:
-                conv(f"up.{lvl}.upsample.conv", c, c, 3)
+        for m in self.layers:
+            if isinstance(m, _ResBlock):
+                resblock(m)
+            elif isinstance(m, _Attn):
+                attn(m)
+            else:
+                conv(m.name, m.c, m.c, 3)
         vec2("norm_out", self.final_ch)
         conv("conv_out", self.out_ch, self.final_ch, 3)
         return s
@@ -196,12 +244,37 @@ class Model(_net.GraphedNet):
 
     def load_state_dict(self, sd, strict=True):
         dev = self.device
-        g = lambda k: sd[k].detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-        w = {}
+        w, memo = {}, {}
+        over = ([], [])              # the launches the first / the second guard objects to, in the order of `s16_launches`
 
-        def s16(t):                 # split-fp16 packing of one weight tensor with its own scale
-            sc = ops.s16_weight_scale(t)
-            return (ops.pack_conv_weight_s16(t, sc), sc, None)
+        def g(k):
+            """Checkpoint tensor `k` as contiguous fp32 on the device, converted once per layer; `<attn>.qkv.*`: the
+            concatenation of q, k and v."""
+            if k not in memo:
+                n, qkv, leaf = k.rpartition(".qkv.")
+                memo[k] = (torch.cat([g(f"{n}.{p}.{leaf}") for p in "qkv"], 0) if qkv else
+                           sd[k].detach().to(device=dev, dtype=torch.float32)).contiguous()
+            return memo[k]
+
+        def layers(seq):             # the conversions are kept for one layer: the load's peak is the packs plus that layer
+            for layer in seq:
+                yield layer
+                memo.clear()
+
+        def split_packs(layer):
+            """The split-fp16 packs of a layer's launches (fp32-grade products on the fp16 matrix pipe,
+            ops.pack_conv_weight_s16) and the guards' verdicts on them, while the layer's tensors are at hand."""
+            for L in self.s16_launches[layer] if self.split16 else ():
+                ws = [g(k + ".weight") for k in L.weights]
+                sc = ops.s16_weight_scale(*ws)
+                w[L.packs[0]] = (ops.pack_conv_weight_s16(ws[0], sc), sc,
+                                 ops.pack_conv_weight_s16(ws[1], sc) if len(ws) > 1 else None)
+                if L.subpixel:
+                    w[L.packs[1]] = ops.upsample_weight_s16(ws[0])
+                if self._guard_normalised_operands(sd, L):
+                    over[0].append(L)
+                if self._guard_weight_range(w, L, ws):
+                    over[1].append(L)
         for k in ("temb.dense.0", "temb.dense.1"):
             w[k + ".weight"], w[k + ".bias"] = g(k + ".weight"), g(k + ".bias")
         w["conv_in.weight"] = ops.pack_conv_weight(g("conv_in.weight"), cin_pad=CIN_PAD)
@@ -211,25 +284,13 @@ class Model(_net.GraphedNet):
             # (stays on the fp32 MFMA tile kernel: the launch is output-store bound -- 268 MB at B = 8 -- and the gather form
             #  of the split arithmetic, with half the workgroups per CU, measured 146 us against 118 us)
         tw, tb = [], []
-        for rb in self.res_blocks:
+        for rb in layers(self.res_blocks):
             n = rb.name
             for norm in ("norm1", "norm2"):
                 w[f"{n}.{norm}.weight"], w[f"{n}.{norm}.bias"] = g(f"{n}.{norm}.weight"), g(f"{n}.{norm}.bias")
             w[f"{n}.conv1.weight"] = ops.pack_conv_weight(g(f"{n}.conv1.weight"))
             w[f"{n}.conv2.weight"] = ops.pack_conv_weight(g(f"{n}.conv2.weight"))
             w[f"{n}.conv2.bias"] = g(f"{n}.conv2.bias")
-            if self.split16:
-                # split-fp16 packing (fp32-grade products on the fp16 matrix pipe, ops.pack_conv_weight_s16); conv2 and
-                # its fused shortcut share an accumulator, hence one scale
-                w1, w2 = g(f"{n}.conv1.weight"), g(f"{n}.conv2.weight")
-                wsk = g(f"{n}.nin_shortcut.weight") if rb.cin != rb.cout else None
-                s1 = ops.s16_weight_scale(w1)
-                s2 = ops.s16_weight_scale(w2) if wsk is None else ops.s16_weight_scale(w2, wsk)
-                w[f"{n}.conv1.s16"] = (ops.pack_conv_weight_s16(w1, s1), s1, None)
-                w[f"{n}.conv2.s16"] = (ops.pack_conv_weight_s16(w2, s2), s2,
-                                       None if wsk is None else ops.pack_conv_weight_s16(wsk, s2))
-                if wsk is not None:
-                    w[f"{n}.nin_shortcut.s16"] = s16(wsk)          # un-fused form (8 x 8 level: gather kernel)
             # conv1 bias folded into the (concatenated) temb projection: h = conv1(.) + b1 + proj(temb)
             tw.append(g(f"{n}.temb_proj.weight"))
             tb.append(g(f"{n}.temb_proj.bias") + g(f"{n}.conv1.bias"))
@@ -239,55 +300,45 @@ class Model(_net.GraphedNet):
                 # fused form: the 1x1 shortcut rides along conv2 as extra K chunks, biases summed
                 w[f"{n}.nin_shortcut.fused"] = ops.pack_skip_weight(g(f"{n}.nin_shortcut.weight"))
                 w[f"{n}.conv2_plus_shortcut.bias"] = (g(f"{n}.conv2.bias") + g(f"{n}.nin_shortcut.bias")).contiguous()
+            split_packs(n)
         w["temb_proj_cat.weight"] = torch.cat(tw, 0).contiguous()
         w["temb_proj_cat.bias"] = torch.cat(tb, 0).contiguous()
-        attns = [a for (_, at, _, _) in self.down for a in at] + [self.mid[1]] + \
-                [a for lvl in self.up for a in self.up[lvl][1]]
-        for a in attns:
+        for a in layers(self.attns):
             n = a.name
             w[f"{n}.norm.weight"], w[f"{n}.norm.bias"] = g(f"{n}.norm.weight"), g(f"{n}.norm.bias")
-            wq = torch.cat([g(f"{n}.{p}.weight") for p in ("q", "k", "v")], 0)
-            w[f"{n}.qkv.weight"] = ops.pack_conv_weight(wq)
-            if self.split16:
-                w[f"{n}.qkv.s16"] = s16(wq)
-                w[f"{n}.proj_out.s16"] = s16(g(f"{n}.proj_out.weight"))
-            w[f"{n}.qkv.bias"] = torch.cat([g(f"{n}.{p}.bias") for p in ("q", "k", "v")], 0).contiguous()
+            for conv in ("qkv", "proj_out"):
+                w[f"{n}.{conv}.weight"], w[f"{n}.{conv}.bias"] = ops.pack_conv_weight(g(f"{n}.{conv}.weight")), g(f"{n}.{conv}.bias")
+            split_packs(n)
             # operand scales of the fused attention kernel (split-fp16 products need |operand| < 2^15): a STATIC bound of the
             # 1x1 convolutions' outputs, |W . GN(x) + b| <= max_o sum_c |W[o, c]| * (sqrt(n) max|gamma| + max|beta|) + max|b|
-            # over the n = H*W*C/32 elements of a group (the bound _guard_normalised_operands uses), as powers of two
-            gmax = math.sqrt(a.res * a.res * max(1, a.c // 32)) * float(sd[f"{n}.norm.weight"].detach().abs().max()) + \
-                float(sd[f"{n}.norm.bias"].detach().abs().max())
+            # (the bound of _guard_normalised_operands), as powers of two; summed on the HOST tensors of `sd`
+            gmax = _gn_bound(sd, n + ".norm", a.res, a.c)
 
             def _pow2(*names):
                 bnd = max(float(sd[f"{n}.{p}.weight"].detach().float().abs().flatten(1).sum(1).max()) * gmax +
                           float(sd[f"{n}.{p}.bias"].detach().abs().max()) for p in names)
                 return 2.0 ** (14 - math.ceil(math.log2(max(bnd, 1e-30))))
             w[f"{n}.attn_scales"] = (_pow2("q", "k"), _pow2("v"))
-            w[f"{n}.proj_out.weight"] = ops.pack_conv_weight(g(f"{n}.proj_out.weight"))
-            w[f"{n}.proj_out.bias"] = g(f"{n}.proj_out.bias")
-        for lvl, (_, _, has_down, c) in enumerate(self.down):
-            if has_down:
-                w[f"down.{lvl}.downsample.conv.weight"] = ops.pack_conv_weight(g(f"down.{lvl}.downsample.conv.weight"))
-                w[f"down.{lvl}.downsample.conv.bias"] = g(f"down.{lvl}.downsample.conv.bias")
-                if self.split16:
-                    w[f"down.{lvl}.downsample.conv.s16"] = s16(g(f"down.{lvl}.downsample.conv.weight"))
-        for lvl, (_, _, has_up, c) in self.up.items():
-            if has_up:
-                w[f"up.{lvl}.upsample.conv.weight"] = ops.pack_conv_weight(g(f"up.{lvl}.upsample.conv.weight"))
-                if self.split16:
-                    wu = g(f"up.{lvl}.upsample.conv.weight")
-                    su = ops.s16_weight_scale(wu)
-                    w[f"up.{lvl}.upsample.conv.s16"] = (ops.pack_conv_weight_s16(wu, su), su, None)
-                    lr = self.resolution >> lvl             # the level's own (low) resolution: 8 x 32 tiles, 64-channel blocks
-                    if c % 64 == 0 and lr % 32 == 0:
-                        w[f"up.{lvl}.upsample.conv.s16_subpixel"] = ops.upsample_weight_s16(wu)
-                w[f"up.{lvl}.upsample.conv.bias"] = g(f"up.{lvl}.upsample.conv.bias")
+        for cv in layers(self.resample):
+            n = cv.name
+            w[n + ".weight"], w[n + ".bias"] = ops.pack_conv_weight(g(n + ".weight")), g(n + ".bias")
+            split_packs(n)
         w["norm_out.weight"], w["norm_out.bias"] = g("norm_out.weight"), g("norm_out.bias")
         w["conv_out.weight"] = ops.pack_conv_weight(g("conv_out.weight"))
         w["conv_out.bias"] = g("conv_out.bias")
         if self.split16:
-            self._guard_normalised_operands(sd, w)
-            self._guard_weight_range(sd, w)
+            # The guards act in two passes, every hit of the first before any of the second.  The first takes a launch's OWN
+            # pack (the operand of a shortcut or of proj_out is not the normalised one); the second takes every pack that
+            # holds the launch's weights, unless the launch's own is gone already: a launch the first guard sent to the fp32
+            # kernel is not judged again, nor is an un-fused shortcut whose pack went with conv2's.
+            self.s16_dropped = [L.name for L in over[0]]
+            for L in over[0]:
+                del w[L.packs[0]]
+            for L in over[1]:
+                if L.packs[0] in w:
+                    for k in L.packs:
+                        w.pop(k, None)
+                    self.s16_dropped.append(L.name)
         half = self.ch // 2
         freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1)))   # models.py:16-17
         w["temb.freq"] = freq.to(dev)
@@ -295,75 +346,26 @@ class Model(_net.GraphedNet):
         self._reset_host_state()
         return self
 
-    def _guard_normalised_operands(self, sd, w):
+    def _guard_normalised_operands(self, sd, L):
         """The split-fp16 kernels scale RAW operands per launch (ops.conv2d, ddnm_conv_desc::amax_in); a GroupNorm'd
         operand carries no run-time bound because it has a static one: |GN(x) * gamma + beta| <= sqrt(n) * max|gamma| +
         max|beta| over the n = H*W*C/32 elements of a group (swish does not increase it).  Checked here, once per
         checkpoint: a norm whose bound does not fit fp16 with a factor 2 to spare sends its consumer to the exact-fp32
         kernel (its split weights are dropped).  No shipped checkpoint is expected to trip this (gamma ~ 1: bound ~ 512);
-        it makes "no operand-range limit" hold for ANY state dict."""
-        groups = 32
-        dropped = []
+        it makes "no operand-range limit" hold for ANY state dict.  True: launch `L` is such a consumer."""
+        return L.norm is not None and _gn_bound(sd, *L.norm) >= 32768.0
 
-        def bound(norm, res, channels):
-            g = sd[norm + ".weight"].detach().abs().max().item()
-            b = sd[norm + ".bias"].detach().abs().max().item()
-            return math.sqrt(res * res * max(1, channels // groups)) * g + b
-        for rb in self.res_blocks:
-            for norm, conv, ch in (("norm1", "conv1", rb.cin), ("norm2", "conv2", rb.cout)):
-                if bound(f"{rb.name}.{norm}", rb.res, ch) >= 32768.0 and w.pop(f"{rb.name}.{conv}.s16", None) is not None:
-                    dropped.append(f"{rb.name}.{conv}")
-        attns = [a for (_, at, _, _) in self.down for a in at] + [self.mid[1]] + [a for lvl in self.up for a in self.up[lvl][1]]
-        for a in attns:
-            if bound(f"{a.name}.norm", a.res, a.c) >= 32768.0 and w.pop(f"{a.name}.qkv.s16", None) is not None:
-                dropped.append(f"{a.name}.qkv")
-        self.s16_dropped = dropped
-        return dropped
-
-    def _guard_weight_range(self, sd, w):
+    def _guard_weight_range(self, w, L, ws):
         """The split-fp16 kernels scale a launch's WEIGHTS by one power of two (ops.s16_weight_scale): a weight far below the
         launch's maximum keeps an absolute error of 2^-25 in scaled units instead of 2^-22 of its own size.  Checked here per
-        launch, on the tensors that share an accumulator: an output row whose summed split error exceeds twice the all-relative
-        value (ops.s16_weight_row_bound > ops.S16_WEIGHT_ROW_LIMIT = 2^-21, derived there) would lose digits against the fp32
-        kernel, so the layer's split weights are dropped and it runs the exact-fp32 kernel.  Appends to `self.s16_dropped`."""
-        g = lambda k: sd[k + ".weight"].detach().to(device=self.device, dtype=torch.float32)  # noqa: E731
-
-        def over(key, *ws):
-            e = w.get(key)
-            return e is not None and ops.s16_weight_row_bound(e[1], *ws) > ops.S16_WEIGHT_ROW_LIMIT
-
-        def drop(name, *keys):
-            if any([w.pop(k, None) is not None for k in keys]) and name not in self.s16_dropped:
-                self.s16_dropped.append(name)
-        for rb in self.res_blocks:
-            n = rb.name
-            if over(n + ".conv1.s16", g(n + ".conv1")):
-                drop(n + ".conv1", n + ".conv1.s16")
-            if rb.cin != rb.cout:
-                # conv2 and its fused shortcut share an accumulator and a scale; the un-fused packing has its own
-                if over(n + ".conv2.s16", g(n + ".conv2"), g(n + ".nin_shortcut")):
-                    drop(n + ".conv2", n + ".conv2.s16", n + ".nin_shortcut.s16")
-                if over(n + ".nin_shortcut.s16", g(n + ".nin_shortcut")):
-                    drop(n + ".nin_shortcut", n + ".nin_shortcut.s16")
-            elif over(n + ".conv2.s16", g(n + ".conv2")):
-                drop(n + ".conv2", n + ".conv2.s16")
-        attns = [a for (_, at, _, _) in self.down for a in at] + [self.mid[1]] + [a for lvl in self.up for a in self.up[lvl][1]]
-        for a in attns:
-            n = a.name
-            if over(n + ".qkv.s16", torch.cat([g(f"{n}.{p}") for p in ("q", "k", "v")], 0)):
-                drop(n + ".qkv", n + ".qkv.s16")
-            if over(n + ".proj_out.s16", g(n + ".proj_out")):
-                drop(n + ".proj_out", n + ".proj_out.s16")
-        for lvl, (_, _, has_down, _) in enumerate(self.down):
-            n = f"down.{lvl}.downsample.conv"
-            if has_down and over(n + ".s16", g(n)):
-                drop(n, n + ".s16")
-        for lvl, (_, _, has_up, _) in self.up.items():
-            n = f"up.{lvl}.upsample.conv"
-            # the sub-pixel form splits the PHASE weights (sums of up to four taps, their own scale): judged on those
-            if has_up and (over(n + ".s16", g(n)) or over(n + ".s16_subpixel", ops.upsample_phase_weights(g(n)))):
-                drop(n, n + ".s16", n + ".s16_subpixel")
-        return self.s16_dropped
+        launch, on the tensors `ws` that share an accumulator: an output row whose summed split error exceeds twice the
+        all-relative value (ops.s16_weight_row_bound > ops.S16_WEIGHT_ROW_LIMIT = 2^-21, derived there) would lose digits
+        against the fp32 kernel, so the layer's split weights are dropped and it runs the exact-fp32 kernel.  True: launch
+        `L`, packed in `w`, is such a layer."""
+        def over(pack, *ws):
+            return ops.s16_weight_row_bound(w[pack][1], *ws) > ops.S16_WEIGHT_ROW_LIMIT
+        # the sub-pixel form splits the PHASE weights (sums of up to four taps, their own scale): judged on those as well
+        return over(L.packs[0], *ws) or (L.subpixel and over(L.packs[1], ops.upsample_phase_weights(ws[0])))
 
     # ------------------------------------------------------------------ forward
     def _max_gn_partials(self):
@@ -427,16 +429,15 @@ class Model(_net.GraphedNet):
         if sc is not None and self.fused_attn and T <= self.fused_attn_max_tokens and ops.attn_fused_supported(T, C):
             # one launch, no [T][T] tensor in HBM (csrc/attn_d512.hip)
             o = ops.attn_fused(qkv, B, T, C, sc[0], sc[1], float(int(C) ** (-0.5))).view(B, H, W, C)
-            return ops.conv2d(o, w[n + ".proj_out.weight"], C, 1, bias=w[n + ".proj_out.bias"], res=x, emit_stats=True,
-                              weight_s16=w.get(n + ".proj_out.s16"))
-        S = torch.empty(B, T, T, dtype=torch.float32, device=qkv.device)
-        q, k, v = qkv.view(-1)[0:], qkv.view(-1)[C:], qkv.view(-1)[2 * C:]
-        ops.bgemm(q, k, S, T, T, C, lda=3 * C, ldb=3 * C, ldc=T, transb=True, batch=B,
-                  sA=(T * 3 * C, 0), sB=(T * 3 * C, 0), sC=(T * T, 0))
-        ops.softmax_rows_(S, B * T, T, T, float(int(C) ** (-0.5)))
-        o = torch.empty(B, H, W, C, dtype=torch.float32, device=qkv.device)
-        ops.bgemm(S, v, o, T, C, T, lda=T, ldb=3 * C, ldc=C, transb=False, batch=B,
-                  sA=(T * T, 0), sB=(T * 3 * C, 0), sC=(T * C, 0))
+        else:
+            S = torch.empty(B, T, T, dtype=torch.float32, device=qkv.device)
+            q, k, v = qkv.view(-1)[0:], qkv.view(-1)[C:], qkv.view(-1)[2 * C:]
+            ops.bgemm(q, k, S, T, T, C, lda=3 * C, ldb=3 * C, ldc=T, transb=True, batch=B,
+                      sA=(T * 3 * C, 0), sB=(T * 3 * C, 0), sC=(T * T, 0))
+            ops.softmax_rows_(S, B * T, T, T, float(int(C) ** (-0.5)))
+            o = torch.empty(B, H, W, C, dtype=torch.float32, device=qkv.device)
+            ops.bgemm(S, v, o, T, C, T, lda=T, ldb=3 * C, ldc=C, transb=False, batch=B,
+                      sA=(T * T, 0), sB=(T * 3 * C, 0), sC=(T * C, 0))
         return ops.conv2d(o, w[n + ".proj_out.weight"], C, 1, bias=w[n + ".proj_out.bias"], res=x, emit_stats=True,
                           weight_s16=w.get(n + ".proj_out.s16"))
 
@@ -491,12 +492,9 @@ class Model(_net.GraphedNet):
                     h = self._attn(attns[ib], h)
             if has_up:
                 n = f"up.{lvl}.upsample.conv"
-                if self._ups_subpixel(n, h.t.shape, c):
-                    h = ops.conv2d(h, w[n + ".weight"], c, 3, bias=w[n + ".bias"], ups=True, emit_stats=True,
-                                   weight_s16=w[n + ".s16_subpixel"], ups_subpixel=True)
-                    continue
+                sub = self._ups_subpixel(n, h.t.shape, c)
                 h = ops.conv2d(h, w[n + ".weight"], c, 3, bias=w[n + ".bias"], ups=True, emit_stats=True,
-                               weight_s16=w.get(n + ".s16"))
+                               weight_s16=w.get(n + (".s16_subpixel" if sub else ".s16")), ups_subpixel=sub)
         gn = self._gn(h, None, "norm_out")
         return ops.conv2d(h, w["conv_out.weight"], self.out_ch, 3, gn=gn, gn_silu=True, bias=w["conv_out.bias"],
                           out_nchw=True)
