@@ -252,6 +252,9 @@ PROTOTYPES = {
     "ddnm_sample_stats_workspace_elems": (c_int64, [c_int32, c_int64]),
     "ddnm_sample_stats_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p]),
+    "ddnm_consistency_workspace_elems": (c_int64, [c_int32, c_int64]),
+    "ddnm_consistency_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_int32, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -13,6 +13,11 @@
 // Sample statistics (ddnm_sample_stats_f32, below the SSIM): the per-pixel mean and standard deviation over the K
 // restorations of one measurement, and their per-image summaries, with the same no-atomics reduction.
 //
+// Data consistency (ddnm_consistency_f32, below the sample statistics): the residual A x^ - y of a finished batch, per
+// image, as sum |d|, sum d^2 (fp64) and max |d| (fp32) over the valid entries of each measurement row -- the one figure of
+// merit that needs no ground truth.  d = (double)ax - (double)y is exact; the per-workgroup partials are added in an order
+// that depends on the row length alone, so a row's three values do not depend on the batch around it either.
+//
 // Why fp64 moments: in fp32 the variance w*x^2 - mu^2 of a flat region cancels to ~1e-7 absolute against C2 = 9e-4,
 // which moves the per-image value by 1e-4 (constant 0.3 vs 0.7; 0.9 vs 0.9 + 1e-3 * noise).  The product of two fp32
 // values is exact in fp64, so x^2, y^2 and xy carry no rounding at all and SSIM(x, x) is exactly 1.  The tile is 16 tall
@@ -269,6 +274,113 @@ __global__ __launch_bounds__(256) void sample_stats_finalize_kernel(const double
     }
 }
 
+// ---------------------------------------------------------------- per-row residual norms of A x^ - y
+// One 256-thread workgroup per CONS_ELEMS consecutive entries of one row; thread t owns the four entries 4 t .. 4 t + 3 of
+// each 1024-entry slab, as in sample_stats_kernel.  Row b has n_b = counts ? counts[b] : m valid entries (clamped to
+// [0, m]); nothing at or beyond n_b is read.  The vector path loads a thread's four entries of both operands with one
+// 16-byte load each where all four are valid and goes element by element over a row's ragged tail; the scalar path goes
+// element by element everywhere -- the same entries in the same order on the same thread, so both give the same bits.
+// Workgroups past n_b write zero partials: the finalize pass adds the same ceil(m / CONS_ELEMS) partials whatever n_b is.
+constexpr int CONS_SLABS = 2;
+constexpr int CONS_ELEMS = CONS_SLABS * 1024;
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void consistency_kernel(const float* __restrict__ ax, const float* __restrict__ y,
+                                                          int64_t row_stride, const int32_t* __restrict__ counts,
+                                                          double* __restrict__ work, int64_t m, int nblk) {
+#pragma clang fp contract(off)
+    __shared__ double red[3][4];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / nblk, blk = blockIdx.x - b * nblk;
+    int64_t nb = counts ? (int64_t)counts[b] : m;
+    nb = nb < 0 ? 0 : (nb > m ? m : nb);
+    const float* ap = ax + (int64_t)b * row_stride;
+    const float* yp = y + (int64_t)b * row_stride;
+    double acc_l1 = 0.0, acc_sse = 0.0, acc_max = 0.0;
+#pragma unroll
+    for (int slab = 0; slab < CONS_SLABS; ++slab) {
+        const int64_t e0 = (int64_t)blk * CONS_ELEMS + slab * 1024 + tid * 4;
+        if (e0 >= nb) continue;
+        const int n = (int)(nb - e0 < 4 ? nb - e0 : 4);
+        float va[4] = {0.0f, 0.0f, 0.0f, 0.0f}, vy[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (VEC && n == 4) {
+            const f32x4 qa = *reinterpret_cast<const f32x4*>(ap + e0);
+            const f32x4 qy = *reinterpret_cast<const f32x4*>(yp + e0);
+            va[0] = qa.x, va[1] = qa.y, va[2] = qa.z, va[3] = qa.w;
+            vy[0] = qy.x, vy[1] = qy.y, vy[2] = qy.z, vy[3] = qy.w;
+        } else {
+            for (int j = 0; j < n; ++j) {
+                va[j] = ap[e0 + j];
+                vy[j] = yp[e0 + j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < n) {
+                const double d = (double)va[j] - (double)vy[j];      // exact: both are fp32
+                const double a = fabs(d);
+                acc_l1 += a;
+                acc_sse += d * d;
+                acc_max = fmax(acc_max, a);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc_l1 += __shfl_xor(acc_l1, o);
+        acc_sse += __shfl_xor(acc_sse, o);
+        acc_max = fmax(acc_max, __shfl_xor(acc_max, o));
+    }
+    if ((tid & 63) == 0) {
+        red[0][tid >> 6] = acc_l1;
+        red[1][tid >> 6] = acc_sse;
+        red[2][tid >> 6] = acc_max;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        work[3 * (int64_t)blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        work[3 * (int64_t)blockIdx.x + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        work[3 * (int64_t)blockIdx.x + 2] = fmax(fmax(red[2][0], red[2][1]), fmax(red[2][2], red[2][3]));
+    }
+}
+
+// l1[b], sse[b] = the sums of the row's `n` partials, in an order that depends on n alone; maxabs[b] = (float) of their max
+// (the max of fp32 differences of fp32 values: |d| < 2^129 may round to inf, as the fp32 subtraction itself would)
+__global__ __launch_bounds__(256) void consistency_finalize_kernel(const double* __restrict__ work, double* __restrict__ l1,
+                                                                   double* __restrict__ sse, float* __restrict__ maxabs,
+                                                                   int n) {
+    __shared__ double red[3][4];
+    const double* w = work + 3 * (int64_t)blockIdx.x * n;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        a0 += w[3 * i];
+        a1 += w[3 * i + 1];
+        a2 = fmax(a2, w[3 * i + 2]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a0 += __shfl_xor(a0, o);
+        a1 += __shfl_xor(a1, o);
+        a2 = fmax(a2, __shfl_xor(a2, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = a0;
+        red[1][threadIdx.x >> 6] = a1;
+        red[2][threadIdx.x >> 6] = a2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        l1[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        sse[blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        maxabs[blockIdx.x] = (float)fmax(fmax(red[2][0], red[2][1]), fmax(red[2][2], red[2][3]));
+    }
+}
+
+// workgroups per row: a function of m alone
+int64_t cons_blocks(int64_t m) {
+    return (m + CONS_ELEMS - 1) / CONS_ELEMS;
+}
+
 // workgroups per image: a function of chw alone, so that an image's partials do not depend on the batch around it
 int64_t stats_blocks(int64_t chw) {
     return (chw + STATS_ELEMS - 1) / STATS_ELEMS;
@@ -354,5 +466,46 @@ extern "C" int ddnm_sample_stats_f32(const float* x, int64_t image_stride, int64
         DDNM_LAUNCH(sample_stats_kernel<false>, grid, dim3(256), 0, st, x, image_stride, sample_stride, x_orig, mean_img,
                     std_img, work, K, chw, nblk);
     DDNM_LAUNCH(sample_stats_finalize_kernel, dim3(B), dim3(256), 0, st, work, sse_mean, std_mean, nblk, (double)chw);
+    return 0;
+}
+
+extern "C" int64_t ddnm_consistency_workspace_elems(int32_t B, int64_t m) {
+    if (B < 1 || m < 1) return DDNM_E_BADARG;
+    const int64_t nblk = cons_blocks(m);
+    if (nblk > INT32_MAX || nblk * B > INT32_MAX) return DDNM_E_SHAPE;      // one workgroup per partial triple, 1-D grid
+    return 3 * nblk * B;
+}
+
+extern "C" int ddnm_consistency_f32(const float* ax, const float* y, int64_t row_stride, const int32_t* counts,
+                                    double* l1, double* sse, float* maxabs, double* work, int64_t work_elems, int32_t B,
+                                    int64_t m, void* stream) {
+    if (!ax || !y || !l1 || !sse || !maxabs || !work || B < 1 || m < 1 || row_stride < m) return DDNM_E_BADARG;
+    const int64_t need = ddnm_consistency_workspace_elems(B, m);
+    if (need < 0) return (int)need;
+    if (work_elems < need) return DDNM_E_SHAPE;
+    if (counts) {
+        // counts in memory the host can read as well (pinned or managed) are checked here; device memory is clamped by
+        // the kernel.  Pageable host memory is refused: the kernel could not read it.
+        hipPointerAttribute_t attr;
+        const hipError_t e = hipPointerGetAttributes(&attr, counts);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return DDNM_E_BADARG;
+        }
+        if (attr.type == hipMemoryTypeUnregistered) return DDNM_E_BADARG;
+        if (attr.type == hipMemoryTypeHost || attr.isManaged) {
+            for (int32_t b = 0; b < B; ++b)
+                if (counts[b] < 0 || counts[b] > m) return DDNM_E_SHAPE;
+        }
+    }
+    const int nblk = (int)cons_blocks(m);
+    const bool vec = row_stride % 4 == 0 && aligned16(ax) && aligned16(y);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)(need / 3));
+    if (vec)
+        DDNM_LAUNCH(consistency_kernel<true>, grid, dim3(256), 0, st, ax, y, row_stride, counts, work, m, nblk);
+    else
+        DDNM_LAUNCH(consistency_kernel<false>, grid, dim3(256), 0, st, ax, y, row_stride, counts, work, m, nblk);
+    DDNM_LAUNCH(consistency_finalize_kernel, dim3(B), dim3(256), 0, st, work, l1, sse, maxabs, nblk);
     return 0;
 }

@@ -174,6 +174,16 @@ class A_functions:
     def singulars(self):
         raise NotImplementedError()
 
+    # ---- what a measurement looks like (host only, nothing is launched): the runner writes y with DDNM_SAVE_Y=1 and
+    # reads it back with --path_y measurements:DIR
+    def measurement_size(self):
+        """Number of valid entries of a row of A(x)."""
+        raise NotImplementedError()
+
+    def measurement_image_shape(self):
+        """(c, h, w) when a row of A(x) is a picture in CHW order that an image file can hold, else None."""
+        return None
+
     # ---- the matrix-free SVD surface (svd_operators.py:16-50).  The sampling path never calls these -- A / A_pinv /
     # Lambda* above are evaluated in their direct forms -- but a drop-in offers them: the BASELINE operators implement
     # V / Vt / U / Ut / add_zeros with the reference's spectral orderings, and At / A_pinv_eta follow from them exactly
@@ -232,6 +242,12 @@ class Denoising(A_functions):
     def A_pinv(self, vec):
         return vec.reshape(vec.shape[0], -1).clone()
 
+    def measurement_size(self):
+        return self.channels * self.img_dim ** 2
+
+    def measurement_image_shape(self):
+        return (self.channels, self.img_dim, self.img_dim)
+
     def singulars(self):
         return torch.ones(self.channels * self.img_dim ** 2, device=self.device)
 
@@ -263,6 +279,12 @@ class SuperResolution(A_functions):
         assert img_dim % ratio == 0
         self.channels, self.img_dim, self.ratio, self.device = channels, img_dim, ratio, device
         self.y_dim = img_dim // ratio
+
+    def measurement_size(self):
+        return self.channels * self.y_dim ** 2
+
+    def measurement_image_shape(self):
+        return (self.channels, self.y_dim, self.y_dim)
 
     def A(self, vec):
         x = _img(vec, self.channels, self.img_dim)
@@ -359,6 +381,12 @@ class Colorization(A_functions):
         self.channels, self.img_dim, self.device = 3, img_dim, device
         self._w = None if weights is None else (ctypes.c_float * 3)(*[float(v) for v in weights])
 
+    def measurement_size(self):
+        return self.img_dim ** 2
+
+    def measurement_image_shape(self):
+        return (1, self.img_dim, self.img_dim)
+
     def A(self, vec):
         x = _img(vec, 3, self.img_dim)
         B, HW = x.shape[0], self.img_dim ** 2
@@ -450,6 +478,13 @@ class Inpainting(A_functions):
         self.kept_mask = keep.float().to(device).contiguous()            # [HW], shared by the 3 channel planes
         self.missing_indices = missing_indices
 
+    def measurement_size(self):
+        return 3 * self.n_kept
+
+    def measurement_image_shape(self):
+        """A full-size picture: the measurement is read from it by applying A (the hole's pixels are ignored)."""
+        return (3, self.img_dim, self.img_dim)
+
     def A(self, vec):
         x = _img(vec, 3, self.img_dim)
         B = x.shape[0]
@@ -540,6 +575,13 @@ class InpaintingBank:
     def __len__(self):
         return len(self.n_kept)
 
+    def measurement_size(self, i):
+        """Valid entries of the measurement row of the image with global index `i` (mask i % N); the row is `y_dim` long."""
+        return 3 * self.n_kept[int(i) % len(self)]
+
+    def measurement_image_shape(self):
+        return (3, self.img_dim, self.img_dim)
+
     def for_images(self, indices):
         """The operator of the images with these global indices, in this order (one index-to-row gather on the device)."""
         rows = [int(i) % len(self) for i in indices]
@@ -565,6 +607,13 @@ class PerImageInpainting(A_functions):
 
     def __len__(self):
         return len(self.n_kept)
+
+    def measurement_size(self):
+        """One number per image of the batch: the rest of each `y_dim`-long row is padding."""
+        return [3 * n for n in self.n_kept]
+
+    def measurement_image_shape(self):
+        return (3, self.img_dim, self.img_dim)
 
     def _check_batch(self, B):
         if B != len(self):
@@ -657,6 +706,9 @@ class WalshHadamardCS(A_functions):
         if self._scratch is None or self._scratch.shape[0] < B:
             self._scratch = torch.empty(B, self.channels, self.N, dtype=torch.float32, device=self.device)
         return self._scratch
+
+    def measurement_size(self):
+        return self.n_keep
 
     def A(self, vec):
         x = _img(vec, self.channels, self.img_dim)
@@ -775,6 +827,9 @@ class CS(A_functions):
     def _npatch(self, B):
         return B * self.channels * self.y_dim ** 2
 
+    def measurement_size(self):
+        return self.channels * self.y_dim ** 2 * self.cs_size
+
     def A(self, vec):
         x = _img(vec, self.channels, self.img_dim)
         B, ps2, cs = x.shape[0], self.ratio ** 2, self.cs_size
@@ -848,6 +903,9 @@ class PixelMask(A_functions):
 
     A_pinv = A
 
+    def measurement_size(self):
+        return self.channels * self.img_dim ** 2
+
 
 class Composition(A_functions):
     """A = A_n ... A_2 A_1 and the reference's "pseudo-inverse" A_1^+ A_2^+ ... A_n^+ of the simplified path's
@@ -866,6 +924,9 @@ class Composition(A_functions):
         for op in reversed(self.parts):
             vec = op.A_pinv(vec)
         return vec
+
+    def measurement_size(self):
+        return self.parts[-1].measurement_size()
 
 
 def mask_color_sr(channels, img_dim, mask, scale, device):
@@ -901,6 +962,9 @@ class GeneralA(A_functions):
 
     def _spectral_dim(self):
         return self._d
+
+    def measurement_size(self):
+        return self._m
 
     @staticmethod
     def _mat_by_vec(M, vec):            # out[b] = M @ vec[b]   (svd_operators.py:174-179)
@@ -1094,6 +1158,12 @@ class SRConv(_SpectralPlus, A_functions):
                   D=y_sub, ldd=m, sD=(m * m, 0), beta=-1.0)
         return y
 
+    def measurement_size(self):
+        return self.channels * self.small_dim ** 2
+
+    def measurement_image_shape(self):
+        return (self.channels, self.small_dim, self.small_dim)
+
     def A(self, vec):
         return self._A(_img(vec, self.channels, self.img_dim))
 
@@ -1187,6 +1257,12 @@ class Deblurring2D(_SpectralPlus, A_functions):
         out = torch.empty(x.shape[0], self.channels * n * n, dtype=torch.float32, device=x.device)
         ops.bgemm(t1, R2_rows, out, n, n, n, lda=n, ldb=n, ldc=n, transb=True, batch=bc, sA=(n * n, 0), sC=(n * n, 0))
         return out
+
+    def measurement_size(self):
+        return self.channels * self.img_dim ** 2
+
+    def measurement_image_shape(self):
+        return (self.channels, self.img_dim, self.img_dim)
 
     def A(self, vec):
         x = _img(vec, self.channels, self.img_dim)

@@ -26,7 +26,16 @@ Deliberate differences at the boundary (not in the results):
   * DDNM_SAMPLES=K (default 1) restores every measurement K times in ONE sampler call, sample k with the noise of a run
     under `--seed seed + k` (sample_sources) and all K with the one measurement y of the run's own seed: `{i}_{k}.png` for
     every k (the reference hard-wires the 0), `mean/mean_{i}.png` (the posterior mean) and `std/std_{i}.png` (the
-    per-pixel standard deviation, ops.sample_stats, csrc/metrics.hip).  The PSNR / SSIM lines stay those of sample 0.
+    per-pixel standard deviation, ops.sample_stats, csrc/metrics.hip).  The PSNR / SSIM lines stay those of sample 0;
+  * measurements leave and enter the process: DDNM_SAVE_Y=1 writes the rows the sampler is given to `y/y_{i}.npy` (+
+    `y/measurements.json`, settings only), and `--path_y measurements:DIR` restores the .npy rows or pictures lying in DIR
+    (MeasurementFolder) instead of degrading a ground truth: no `orig_{i}.png`, no PSNR / SSIM.  With the same seed and
+    settings the second run writes the first run's PNGs byte for byte (not under DDNM_NOISE=torch, not for the two CS
+    operators, whose matrices come from the global generators);
+  * DDNM_METRICS=cons reports the data consistency of every restoration, the one figure of merit that needs no ground
+    truth (and the one a run over given measurements reports unasked): `Cons: %.3e`, the running mean of
+    sum |A x^ - y| / (2 n) over the n valid entries of an image's measurement ([0, 1] scale), `Total Average Cons` and
+    `Max Cons`, the largest max |A x^ - y| / 2 of the run (ops.consistency, csrc/metrics.hip).
 
 All of these run through ONE path of `Diffusion.svd_based_ddnm_plus`: the plan (`fuse_groups`: which loader batches this
 rank restores, grouped into sampler calls; `restored_images` is the same plan as image indices), `prepare` (a loader batch
@@ -170,6 +179,161 @@ class SyntheticImages(data.Dataset):
         return torch.rand(3, self.size, self.size, generator=g), 0
 
 
+MEASUREMENTS = "measurements:"                      # --path_y measurements:DIR: restore the measurements lying in DIR
+MEASUREMENT_EXT = (".npy", ".png", ".jpg", ".jpeg")
+MEASUREMENT_SETTINGS = "measurements.json"          # what DDNM_SAVE_Y=1 writes next to the y_{i}.npy: settings only
+MEASUREMENT_PINNED = ("deg", "deg_scale", "image_size", "channels")      # a folder's settings a run must agree with
+
+
+def measurement_dir(path_y, exp):
+    """DIR of `--path_y measurements:DIR` (absolute, or below <exp>/datasets/), None for every other --path_y."""
+    path_y = str(path_y)
+    if not path_y.startswith(MEASUREMENTS):
+        return None
+    d = path_y[len(MEASUREMENTS):]
+    if not d:
+        raise ValueError(f"--path_y {path_y}: name the folder of measurements after the colon")
+    return d if os.path.isabs(d) else os.path.join(exp, "datasets", d)
+
+
+# DDNM_SAVE_Y=1: the SVD-path runner writes the measurement rows it restores from to <image_folder>/y/ (default: off)
+def save_y():
+    v = os.environ.get("DDNM_SAVE_Y", "")
+    if v not in ("", "0", "1"):
+        raise ValueError(f"DDNM_SAVE_Y must be 0 or 1, got {v!r}")
+    return v == "1"
+
+
+def run_settings(args, config, sigma_y):
+    """The settings a saved measurement depends on (`sigma_y` on the command line's [0, 1] scale)."""
+    return {"deg": args.deg, "deg_scale": float(args.deg_scale), "image_size": int(config.data.image_size),
+            "channels": int(config.data.channels), "sigma_y": float(sigma_y), "add_noise": bool(args.add_noise),
+            "seed": int(args.seed)}
+
+
+def check_measurements(args, simplified):
+    """What a run over given measurements (`--path_y measurements:DIR`) cannot do, said before its first image is loaded."""
+    if measurement_dir(args.path_y, args.exp) is None:
+        return
+    if args.add_noise:
+        raise ValueError("--add_noise with --path_y measurements:DIR: the measurement is given, there is nothing to add "
+                         "noise to (--sigma_y alone states its noise level and selects DDNM+)")
+    if "ssim" in extra_metrics():
+        raise ValueError("DDNM_METRICS=ssim with --path_y measurements:DIR: SSIM compares with the ground truth, and a "
+                         "run over given measurements has none (Cons is reported instead)")
+    if simplified:
+        raise ValueError("--simplified with --path_y measurements:DIR: measurements are read by the SVD path only")
+
+
+def _last_int_key(name):
+    """Sort key of a measurement file: the last integer of its stem, then the name (y_2 before y_10); stems without a
+    digit follow, by name."""
+    stem = os.path.splitext(name)[0]
+    digits = ""
+    for ch in reversed(stem):
+        if ch.isdigit():
+            digits = ch + digits
+        elif digits:
+            break
+    return (0, int(digits), name) if digits else (1, 0, name)
+
+
+class MeasurementFolder(data.Dataset):
+    """The measurements of `--path_y measurements:DIR`: the .npy / .png / .jpg / .jpeg files of DIR (not
+    measurements.json), ordered by the last integer of the stem, then by name; position p is image --subset_start + p.
+    `bind(op, config, start)` names the operator the rows belong to and checks every file against it (element count of
+    an .npy, pixel size of a picture) before anything is restored.  An item is (tensor, is_picture): an .npy gives its
+    row as it is -- any shape with `measurement_size` elements, cast to fp32, zero padded to a mask bank's y_dim --, a
+    picture gives [c, h, w] of `measurement_image_shape()` on the engine's [-1, 1] scale (the runner flattens it, or
+    applies A for inpainting).  Nothing is resized, cropped or shuffled."""
+
+    def __init__(self, root, limit=None):
+        if not os.path.isdir(root):
+            raise FileNotFoundError(f"no folder of measurements at {root}")
+        names = [f for f in os.listdir(root)
+                 if f.lower().endswith(MEASUREMENT_EXT) and os.path.isfile(os.path.join(root, f))]
+        names.sort(key=_last_int_key)
+        stems = {}
+        for f in names:
+            stem = os.path.splitext(f)[0]
+            if stem in stems:
+                raise ValueError(f"{root}: {stems[stem]} and {f} share the stem {stem!r}: one measurement per image")
+            stems[stem] = f
+        if not names:
+            raise FileNotFoundError(f"no measurements (.npy, .png, .jpg, .jpeg) in {root}")
+        self.root, self.names = root, names[:limit]
+        self.op = self.config = None
+        self.start = 0
+
+    def settings(self):
+        """The folder's measurements.json as a dict, None without the file."""
+        import json
+        path = os.path.join(self.root, MEASUREMENT_SETTINGS)
+        if not os.path.exists(path):
+            return None
+        with open(path) as f:
+            return json.load(f)
+
+    def check_settings(self, run):
+        """`run` (run_settings) against the folder's measurements.json: the operator must be the one y was formed with."""
+        have = self.settings()
+        for key in MEASUREMENT_PINNED if have else ():
+            if key in have and have[key] != run[key]:
+                raise ValueError(f"{os.path.join(self.root, MEASUREMENT_SETTINGS)}: the measurements were formed with "
+                                 f"{key} = {have[key]!r}, this run has {key} = {run[key]!r}")
+
+    def __len__(self):
+        return len(self.names)
+
+    def _expected(self, p):
+        """(valid entries, row length) of the measurement at position p."""
+        if hasattr(self.op, "for_images"):                     # a mask bank: image i uses mask i % N
+            return self.op.measurement_size(self.start + p), self.op.y_dim
+        n = self.op.measurement_size()
+        return n, n
+
+    def bind(self, op, config, start=0):
+        self.op, self.config, self.start = op, config, start
+        shape = op.measurement_image_shape()
+        for p, f in enumerate(self.names):
+            path, n = os.path.join(self.root, f), self._expected(p)[0]
+            if f.lower().endswith(".npy"):
+                arr = np.load(path, mmap_mode="r", allow_pickle=False)
+                if arr.size != n:
+                    raise ValueError(f"{path} holds {arr.size} values (shape {tuple(arr.shape)}), the operator's measurement "
+                                     f"of image {start + p} has {n}")
+            elif shape is None:
+                raise ValueError(f"{path} is a picture, but a measurement of this operator is no picture: it takes .npy "
+                                 f"files of {n} values")
+            elif shape[0] not in (1, 3):
+                raise ValueError(f"{path}: pictures hold 1 or 3 channels, the operator's measurement has {shape[0]}")
+            else:
+                from PIL import Image
+                with Image.open(path) as img:
+                    w, h = img.size
+                if (h, w) != tuple(shape[1:]):
+                    raise ValueError(f"{path} is {w} x {h} pixels (width x height), the operator's measurement is "
+                                     f"{shape[2]} x {shape[1]}: nothing is resized or cropped")
+        return self
+
+    def __getitem__(self, p):
+        if self.op is None:
+            raise RuntimeError("MeasurementFolder.bind(operator, config) comes first")
+        f = self.names[p]
+        path = os.path.join(self.root, f)
+        if f.lower().endswith(".npy"):
+            n, width = self._expected(p)
+            row = torch.zeros(width, dtype=torch.float32)
+            row[:n] = torch.from_numpy(np.load(path, allow_pickle=False).astype(np.float32).reshape(-1))
+            return row, False
+        from PIL import Image
+        c = self.op.measurement_image_shape()[0]
+        with Image.open(path) as img:
+            arr = np.asarray(img.convert("L" if c == 1 else "RGB"), dtype=np.uint8)
+        x = torch.from_numpy(arr.reshape(arr.shape[0], arr.shape[1], c).copy()).permute(2, 0, 1).float().div(255.0)
+        return data_transform(self.config, x).contiguous(), True
+
+
 def save_image(x, path):
     """torchvision.utils.save_image for one [3,H,W] image in [0,1]."""
     from PIL import Image
@@ -306,7 +470,7 @@ STD_DISPLAY_GAIN = 4.0      # std/std_{i}.png holds clamp(gain * s, 0, 1): a dis
 
 
 # DDNM_METRICS: comma-separated metrics reported NEXT TO the PSNR (unset / empty = PSNR alone, today's output)
-METRICS = ("ssim",)
+METRICS = ("ssim", "cons")
 SSIM_MIN_SIZE = 11          # the 11x11 window needs one valid position
 
 
@@ -329,8 +493,14 @@ class MetricLog:
     of `Apy/orig_{i}.png`); the simplified runner writes that image's restoration as `{i - 1}_0.png`, like the
     reference."""
 
-    def __init__(self, image_size, samples=1):
-        self.with_ssim = "ssim" in extra_metrics(image_size)
+    def __init__(self, image_size, samples=1, ground_truth=True):
+        names = extra_metrics(image_size)
+        self.with_ssim = "ssim" in names
+        # Cons (DDNM_METRICS=cons, and unasked in a run without ground truth, whose only figure of merit it is): per image
+        # l1 / (2 n), the mean absolute residual of A x^ - y on the [0, 1] scale, and ConsMax = maxabs / 2 (add_cons)
+        self.ground_truth = ground_truth
+        self.with_cons = "cons" in names or not ground_truth
+        self.cons_sum, self.all_cons_sum, self.cons_max, self.cons = 0.0, 0.0, 0.0, []
         self.psnr_sum, self.ssim_sum, self.n = 0.0, 0.0, 0
         self.index, self.psnr, self.ssim = [], [], []
         # DDNM_SAMPLES=K > 1: the posterior-mean image, all K samples, the mean standard deviation (add_samples)
@@ -350,13 +520,36 @@ class MetricLog:
             self.ssim_sum += float(s.sum())
             self.ssim += s.cpu().tolist()
             print("SSIM: %.4f" % (self.ssim_sum / self.n))
+        elif self.with_cons:
+            self.index += range(idx0, idx0 + b)
+
+    def count(self, b, idx0):
+        """One finished loader batch of a run without ground truth: no PSNR / SSIM line, the images are counted."""
+        self.n += b
+        self.index += range(idx0, idx0 + b)
+
+    def add_cons(self, l1, maxabs, sizes, sample):
+        """ops.consistency's `l1`, `maxabs` [b] of sample `sample` of the loader batch `add` / `count` has just counted;
+        `sizes` [b]: valid entries of each measurement row.  Sample 0 prints the `Cons:` line (running mean)."""
+        cons = l1.double().cpu() / (2.0 * torch.tensor([float(n) for n in sizes], dtype=torch.float64))
+        self.all_cons_sum += float(cons.sum())
+        self.cons_max = max(self.cons_max, float(maxabs.max()) / 2.0)
+        if sample == 0:
+            self.cons_sum += float(cons.sum())
+            self.cons += cons.tolist()
+            print("Cons: %.3e" % (self.cons_sum / self.n))
+        if self.samples > 1 and sample == self.samples - 1:
+            print("Sample Cons: %.3e" % (self.all_cons_sum / (self.n * self.samples)))
 
     def add_samples(self, psnr_mean, psnr_all, std_mean, mean_img, x_orig):
         """The K-sample figures of the loader batch `add` has just counted (sample 0): `psnr_mean`, `std_mean` [b] and
         `mean_img` ([0, 1] scale) from ops.sample_stats, `psnr_all` [K, b] of every sample, x_orig on the [-1, 1] scale."""
+        self.std_sum += float(std_mean.sum())
+        if not self.ground_truth:                # no x_orig: the spread of the samples is all there is to say
+            print("Std: %.4f" % (self.std_sum / self.n))
+            return
         self.mean_psnr_sum += float(psnr_mean.sum())
         self.all_psnr_sum += float(psnr_all.double().sum())
-        self.std_sum += float(std_mean.sum())
         print("Mean-of-K PSNR: %.2f" % (self.mean_psnr_sum / self.n))
         print("Sample PSNR: %.2f" % (self.all_psnr_sum / (self.n * self.samples)))
         print("Std: %.4f" % (self.std_sum / self.n))
@@ -376,31 +569,50 @@ class MetricLog:
                 self.std_sum = ddist.reduce_sum(self.std_sum, device)
                 if self.with_ssim:
                     self.mean_ssim_sum = ddist.reduce_sum(self.mean_ssim_sum, device)
+        if reduce and self.with_cons:
+            self.cons_sum = ddist.reduce_sum(self.cons_sum, device)
+            self.all_cons_sum = ddist.reduce_sum(self.all_cons_sum, device)
+            self.cons_max = ddist.reduce_scalar(self.cons_max, device, "max")
         n = max(self.n, 1)
         if rank == 0:
-            print("Total Average PSNR: %.2f" % (self.psnr_sum / n))
+            if self.ground_truth:
+                print("Total Average PSNR: %.2f" % (self.psnr_sum / n))
             if self.with_ssim:
                 print("Total Average SSIM: %.4f" % (self.ssim_sum / n))
-            if self.samples > 1:
+            if self.with_cons:
+                print("Total Average Cons: %.3e" % (self.cons_sum / n))
+                print("Max Cons: %.3e" % self.cons_max)
+            if self.samples > 1 and self.ground_truth:
                 print("Total Average Mean-of-K PSNR: %.2f" % (self.mean_psnr_sum / n))
                 print("Total Average Sample PSNR: %.2f" % (self.all_psnr_sum / (n * self.samples)))
                 print("Total Average Std: %.4f" % (self.std_sum / n))
                 if self.with_ssim:
                     print("Total Average Mean-of-K SSIM: %.4f" % (self.mean_ssim_sum / n))
+            if self.samples > 1 and not self.ground_truth:
+                print("Total Average Std: %.4f" % (self.std_sum / n))
+            if self.samples > 1 and self.with_cons:
+                print("Total Average Sample Cons: %.3e" % (self.all_cons_sum / (n * self.samples)))
             print("Number of samples: %d" % self.n)
             if self.samples > 1:
                 print("Samples per image: %d" % self.samples)
         extra = {}
         if self.samples > 1:
-            extra = {"samples": self.samples, "psnr_mean_image": self.mean_psnr_sum / n,
-                     "psnr_all_samples": self.all_psnr_sum / (n * self.samples), "std": self.std_sum / n}
+            extra = {"samples": self.samples, "psnr_mean_image": self.mean_psnr_sum / n if self.ground_truth else None,
+                     "psnr_all_samples": self.all_psnr_sum / (n * self.samples) if self.ground_truth else None,
+                     "std": self.std_sum / n}
             if self.with_ssim:
                 extra["ssim_mean_image"] = self.mean_ssim_sum / n
+        if self.with_cons:      # the keys of a run that reports Cons; the runner's last_metrics holds None for the first two without
+            extra.update(cons=self.cons_sum / n, cons_max=self.cons_max, cons_per_image=self.cons)
+            if self.samples > 1:
+                extra["cons_all_samples"] = self.all_cons_sum / (n * self.samples)
         return {**self._totals(n), **extra}
 
     def _totals(self, n):
-        return {"psnr": self.psnr_sum / n, "ssim": self.ssim_sum / n if self.with_ssim else None, "n": self.n,
-                "index": self.index if self.with_ssim else None, "psnr_per_image": self.psnr if self.with_ssim else None,
+        lists = self.with_ssim or self.with_cons
+        return {"psnr": self.psnr_sum / n if self.ground_truth else None,
+                "ssim": self.ssim_sum / n if self.with_ssim else None, "n": self.n,
+                "index": self.index if lists else None, "psnr_per_image": self.psnr if self.with_ssim else None,
                 "ssim_per_image": self.ssim if self.with_ssim else None}
 
 
@@ -450,7 +662,10 @@ def rank_slice(b, batch_size, rank, world):
 # batch's first image, batch size `b`, this rank's images [lo, hi) of it, `x_orig` [b] on the [-1, 1] scale, the
 # measurement rows `y` [hi - lo], `x_T` [NS * (hi - lo)] ordered [sample k][image j], and `noise`: one source per sample
 # (ops.PhiloxNoise with image_base = lo, or a BatchNoise tape under DDNM_NOISE=torch)
-Part = collections.namedtuple("Part", "bi idx0 b lo hi x_orig y x_T noise")
+# For the writer's Cons and y/ files the part also keeps the whole batch: its measurement rows `y_all` [b], its operator `op`
+# and the number of valid entries of every row, `valid` [b] (a mask bank pads its rows).  A run over given measurements has
+# x_orig None.
+Part = collections.namedtuple("Part", "bi idx0 b lo hi x_orig y x_T noise y_all op valid")
 
 
 def _cat(tensors):
@@ -531,6 +746,8 @@ class Diffusion(object):
 
     def sample(self, simplified):
         check_samples(samples(), simplified)
+        check_measurements(self.args, simplified)
+        save_y()
         model = self._build_model()
         # batch sizes of 1 and 2 (the reference's shipped `sampling.batch_size: 1`) replay the forward from a hipGraph:
         # eager, the host needs longer to enqueue a forward's ~250-300 launches than the GPU to run them
@@ -549,6 +766,9 @@ class Diffusion(object):
     # ------------------------------------------------------------------ data
     def _loader(self):
         args, config = self.args, self.config
+        mdir = measurement_dir(args.path_y, args.exp)
+        if mdir is not None:
+            return self._measurement_loader(mdir)
         if str(args.path_y).startswith("synthetic"):
             n = int(str(args.path_y).split(":")[1]) if ":" in str(args.path_y) else config.sampling.batch_size
             ds = SyntheticImages(n, config.data.image_size, args.seed)
@@ -601,11 +821,29 @@ class Diffusion(object):
         return data.DataLoader(ds, batch_size=config.sampling.batch_size, shuffle=True, num_workers=0,
                                worker_init_fn=seed_worker, generator=g)
 
+    def _measurement_loader(self, root):
+        """The loader of `--path_y measurements:DIR`: the folder's entries in their own order (no celeba index shuffle, no
+        loader shuffle), position p = image --subset_start + p, at most --subset_end - --subset_start of them.  A batch
+        is the list of its items (rows and pictures do not stack); the operator is bound by the SVD path."""
+        args, config = self.args, self.config
+        limit = None
+        if args.subset_start >= 0 and args.subset_end > 0:
+            assert args.subset_end > args.subset_start
+            limit = args.subset_end - args.subset_start
+        ds = MeasurementFolder(root, limit)
+        ds.check_settings(run_settings(args, config, args.sigma_y))
+        if limit is None:
+            args.subset_start, args.subset_end = 0, len(ds)
+        print(f"Dataset has size {len(ds)}")
+        return data.DataLoader(ds, batch_size=config.sampling.batch_size, shuffle=False, num_workers=0, collate_fn=list)
+
     # ------------------------------------------------------------------ SVD path (diffusion.py:419-610)
     def _write_apy(self, A_funcs, y, x_orig, idx0):
         """`Apy/Apy_{i}.png` (A^+ y, or what the reference shows in its place for the task) and `Apy/orig_{i}.png` of one
-        loader batch whose first image has the global index `idx0`."""
-        args, (b, C, S, _) = self.args, x_orig.shape
+        loader batch whose first image has the global index `idx0` (`x_orig` None, a run over given measurements: no
+        orig file)."""
+        args, config = self.args, self.config
+        b, C, S = y.shape[0], config.data.channels, config.data.image_size
         Apy = A_funcs.A_pinv(y).view(b, C, S, S)
         if args.deg[:6] == "deblur":
             Apy = y.view(b, C, S, S)
@@ -616,12 +854,19 @@ class Diffusion(object):
         for i in range(b):
             save_image(ops.finalize_psnr(Apy[i:i + 1].contiguous())[0][0],
                        os.path.join(args.image_folder, f"Apy/Apy_{idx0 + i}.png"))
-            save_image(ops.finalize_psnr(x_orig[i:i + 1])[0][0], os.path.join(args.image_folder, f"Apy/orig_{idx0 + i}.png"))
+            if x_orig is not None:
+                save_image(ops.finalize_psnr(x_orig[i:i + 1])[0][0],
+                           os.path.join(args.image_folder, f"Apy/orig_{idx0 + i}.png"))
 
     def svd_based_ddnm_plus(self, model, cls_fn):
         args, config = self.args, self.config
         loader = self._loader()
         A_funcs = build_operator(args.deg, args.deg_scale, config, self.device)
+        # --path_y measurements:DIR: y is given, there is no x_orig; every file is checked against the operator here
+        measured = isinstance(loader.dataset, MeasurementFolder)
+        if measured:
+            loader.dataset.bind(A_funcs, config, args.subset_start)
+        settings = run_settings(args, config, args.sigma_y)
         args.sigma_y = 2 * args.sigma_y          # scaling to [-1, 1] (:524)
         sigma_y = args.sigma_y
         rank, world = ddist.world_state()      # the INITIALISED group (env-only sharding without a group loses shards)
@@ -630,8 +875,17 @@ class Diffusion(object):
         # DDNM_SAMPLES=NS: every measurement restored NS times in one sampler call, rows [sample k][image j], sample k with
         # the noise of a run under --seed seed + k and all of them with the one y of this run (NS = 1: the plain run)
         NS = samples()
-        log = MetricLog(S, NS)
+        log = MetricLog(S, NS, ground_truth=not measured)
         os.makedirs(os.path.join(args.image_folder, "Apy"), exist_ok=True)      # (rank 0 made the image folder before the first barrier)
+        # DDNM_SAVE_Y=1: the rows the sampler is given go to y/y_{i}.npy (written by the rank that writes Apy_{i}.png), the
+        # settings they were formed with to y/measurements.json (rank 0, once)
+        keep_y = save_y()
+        if keep_y:
+            import json
+            os.makedirs(os.path.join(args.image_folder, "y"), exist_ok=True)
+            if rank == 0:
+                with open(os.path.join(args.image_folder, "y", MEASUREMENT_SETTINGS), "w") as f:
+                    json.dump(settings, f, indent=1)
         if NS > 1:
             os.makedirs(os.path.join(args.image_folder, "mean"), exist_ok=True)
             os.makedirs(os.path.join(args.image_folder, "std"), exist_ok=True)
@@ -657,12 +911,24 @@ class Diffusion(object):
         # a mask bank (3-D mask.npy): every operator is built for the images of ITS rows, image i using mask i % N
         bank = A_funcs if isinstance(A_funcs, InpaintingBank) else None
 
-        def prepare(bi, x_orig):
+        def given(items, A_batch):
+            """The measurement rows [b, m] of a batch of MeasurementFolder items: an .npy row as it is, a picture
+            flattened -- or, for inpainting, passed through A, which reads the kept pixels and pads a bank's row."""
+            rows = []
+            for j, (t, picture) in enumerate(items):
+                t = t.to(self.device)
+                if picture and args.deg == "inpainting":
+                    t = (A_batch if bank is None else A_batch.narrow(j, j + 1)).A(t[None].contiguous())
+                rows.append(t.reshape(1, -1))
+            return _cat(rows).contiguous()
+
+        def prepare(bi, batch):
             """The Part of loader batch `bi`: y = A x_orig of the whole batch (operators are cheap, and the writer needs
-            A^+ y of all: the Apy/ files), x_T and the noise sources of this rank's images [lo, hi) for every sample."""
-            idx0, b = first[bi], x_orig.shape[0]
+            A^+ y of all: the Apy/ files) -- or the given y of a run over measurements, which has no x_orig --, x_T and
+            the noise sources of this rank's images [lo, hi) for every sample."""
+            idx0, b = first[bi], len(batch)
             # (split mode: every rank sees the same batch -- same loader seed; rank r restores images [lo, hi) of it)
-            x_orig = data_transform(config, x_orig.to(self.device)).contiguous()
+            x_orig = None if measured else data_transform(config, batch.to(self.device)).contiguous()
             lo, hi = rank_slice(b, batch_size, rank, world)
             if philox:
                 # no ATen RNG launch in the loop, nothing drawn for other ranks' images: key = (seed + sample, batch),
@@ -674,7 +940,7 @@ class Diffusion(object):
                 noise = [BatchNoise(args.seed + k, bi, b, (C, S, S), lo, hi, self.device) for k in range(NS)]
                 x_T = _cat([tape.x_T() for tape in noise])
             A_batch = A_funcs if bank is None else bank.for_images(range(idx0, idx0 + b))
-            y = A_batch.A(x_orig)
+            y = given(batch, A_batch) if measured else A_batch.A(x_orig)
             if args.add_noise:
                 if philox:
                     y = y + measurement_noise(_mix64(args.seed, bi) ^ 0x5DEECE66D, y.reshape(b, -1)).reshape(y.shape) * sigma_y
@@ -684,7 +950,13 @@ class Diffusion(object):
                         tape.draw(tuple(y.shape))    # the samples share y; each tape still moves as in its own run
             if writer:
                 self._write_apy(A_batch, y, x_orig, idx0)
-            return Part(bi, idx0, b, lo, hi, x_orig, y.reshape(b, -1)[lo:hi].contiguous(), x_T, noise)
+            y_all = y.reshape(b, -1)
+            valid = A_batch.measurement_size() if bank is not None else [y_all.shape[1]] * b
+            if writer and keep_y:
+                rows = y_all.cpu().numpy()
+                for j in range(b):
+                    np.save(os.path.join(args.image_folder, "y", f"y_{idx0 + j}.npy"), rows[j, :valid[j]])
+            return Part(bi, idx0, b, lo, hi, x_orig, y_all[lo:hi].contiguous(), x_T, noise, y_all, A_batch, valid)
 
         def restore(parts):
             """ONE sampler call for the loader batches `parts` (one batch, or a fused group), rows batch-major, then
@@ -733,25 +1005,34 @@ class Diffusion(object):
                 img, psnr = ops.finalize_psnr(x_k, p.x_orig)
                 for j in range(p.b):
                     save_image(img[j], os.path.join(args.image_folder, f"{p.idx0 + j}_{k}.png"))
-                if k == 0:
+                if k == 0 and measured:
+                    log.count(p.b, p.idx0)
+                elif k == 0:
                     log.add(x_k, p.x_orig, psnr, p.idx0)
                 psnr_all.append(psnr)
+                if log.with_cons:
+                    # A applied to the sampler's final tensor (unclamped, [-1, 1] scale) against the y it was given
+                    l1, _, maxabs = ops.consistency(p.op.A(x_k).reshape(p.b, -1), p.y_all,
+                                                    p.valid if bank is not None else None)
+                    log.add_cons(l1, maxabs, p.valid, k)
             if NS > 1:
                 mean_img, std_img, psnr_mean, std_mean = ops.sample_stats(x_rows, p.b, NS, layout, p.x_orig)
                 std_shown = (std_img * STD_DISPLAY_GAIN).clamp_(0.0, 1.0)
                 for j in range(p.b):
                     save_image(mean_img[j], os.path.join(args.image_folder, f"mean/mean_{p.idx0 + j}.png"))
                     save_image(std_shown[j], os.path.join(args.image_folder, f"std/std_{p.idx0 + j}.png"))
-                log.add_samples(psnr_mean, torch.stack(psnr_all), std_mean, mean_img, p.x_orig)
+                log.add_samples(psnr_mean, None if measured else torch.stack(psnr_all), std_mean, mean_img, p.x_orig)
 
         group = []
-        for bi, x_orig in ((bi, x) for bi, (x, _) in enumerate(loader) if bi in first):      # the batches of the plan
-            group.append(prepare(bi, x_orig))
+        # the batches of the plan: the images of a ground-truth batch, the list of items of a batch of given measurements
+        for bi, batch in ((bi, x if measured else x[0]) for bi, x in enumerate(loader) if bi in first):
+            group.append(prepare(bi, batch))
             if bi in ends:
                 for p, x_rows in zip(group, restore(group)):     # one PSNR line per loader batch, in loader order
                     finish(p, x_rows)
                 group = []
-        self.last_metrics = log.total(rank, self.device, reduce=deal)
+        # (cons / cons_max: None unless Cons was reported; psnr: None in a run over given measurements)
+        self.last_metrics = {"cons": None, "cons_max": None, **log.total(rank, self.device, reduce=deal)}
         ddist.barrier()
         return self.last_metrics["psnr"]
 
@@ -798,11 +1079,15 @@ class Diffusion(object):
         group_ends = {g[-1][0] for g in fuse_groups(len(loader.dataset), 1, rank, world, K)} if K > 1 else set()
         pending = []
 
-        def finish(x, x_orig, idx0):
+        def finish(x, x_orig, idx0, y):
             img, psnr = ops.finalize_psnr(x, x_orig)
             # the reference names the file with the stale loop variable j = -1 (:402); reproduced
             save_image(img[0], os.path.join(args.image_folder, f"{idx0 + (-1)}_{0}.png"))
             log.add(x, x_orig, psnr, idx0)
+            if log.with_cons:
+                y = y.reshape(1, -1).contiguous()
+                l1, _, maxabs = ops.consistency(op.A(x).reshape(1, -1).contiguous(), y)
+                log.add_cons(l1, maxabs, [y.shape[1]], 0)
 
         for bi, (x_orig, classes) in enumerate(loader):
             if config.sampling.batch_size != 1:
@@ -825,13 +1110,13 @@ class Diffusion(object):
                                          torch.cat([p[1] for p in pending], 0), sigma_y, config,
                                          noise=FusedTape([p[2] for p in pending]))
                     for j, p in enumerate(pending):
-                        finish(xf[j:j + 1].contiguous(), p[3], p[4])
+                        finish(xf[j:j + 1].contiguous(), p[3], p[4], p[1])
                     pending = []
             else:
                 x = simplified_loop(x, model, self.betas, args.eta, op, y, sigma_y, config)
-                finish(x, x_orig, idx_so_far)
+                finish(x, x_orig, idx_so_far, y)
             idx_so_far += y.shape[0]
-        self.last_metrics = log.total(rank, self.device, reduce=True)
+        self.last_metrics = {"cons": None, "cons_max": None, **log.total(rank, self.device, reduce=True)}
         return self.last_metrics["psnr"]
 
 

@@ -1187,3 +1187,45 @@ def sample_stats(x, n_images, n_samples, layout="samples_major", x_orig=None):
           "ddnm_sample_stats_f32")
     psnr = 10.0 * torch.log10(1.0 / (sse / chw)) if sse is not None else None
     return mean_img, std_img, psnr, std_mean
+
+
+def consistency(ax, y, counts=None):
+    """Per-row norms of the residual `ax - y` of two [B, m] measurement tensors (csrc/metrics.hip::ddnm_consistency_f32):
+    returns (l1, sse, maxabs) = (sum |d|, sum d^2, max |d|) over the first `counts[b]` entries of row b (all m without
+    `counts`: a length-B sequence or int32 tensor inside [0, m]; a mask bank pads its rows) as float64 / float64 / float32
+    tensors [B].  The differences are formed in fp64 (exact) and a row's values do not depend on the batch around it."""
+    if not (torch.is_tensor(ax) and torch.is_tensor(y)) or ax.dim() != 2 or ax.shape != y.shape:
+        raise ValueError("consistency: expected two [B, m] tensors of one shape, got "
+                         f"{tuple(ax.shape) if torch.is_tensor(ax) else type(ax).__name__} and "
+                         f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+    B, m = ax.shape
+    if B < 1 or m < 1:
+        raise ValueError(f"consistency: need at least one row and one entry, got {B} rows of {m}")
+    if counts is not None:
+        if torch.is_tensor(counts):
+            if counts.dtype != torch.int32 or counts.dim() != 1:
+                raise ValueError(f"consistency: counts must be a 1-D int32 tensor, got {counts.dtype} {tuple(counts.shape)}")
+            host = counts.cpu().tolist()
+        else:
+            host = list(counts)
+            if any(int(c) != c for c in host):
+                raise ValueError(f"consistency: counts must be whole numbers, got {host}")
+            host = [int(c) for c in host]
+        if len(host) != B:
+            raise ValueError(f"consistency: {len(host)} counts for {B} rows")
+        if min(host) < 0 or max(host) > m:
+            raise ValueError(f"consistency: counts must lie in [0, {m}], got {host}")
+        if not (torch.is_tensor(counts) and counts.is_cuda and counts.is_contiguous()):
+            counts = torch.tensor(host, dtype=torch.int32).to(ax.device)
+    ax, y = _f32c(ax, "ax"), _f32c(y, "y")
+    lib = _lib.lib()
+    n = lib.ddnm_consistency_workspace_elems(B, m)
+    if n < 0:
+        check(int(n), "ddnm_consistency_workspace_elems")
+    work = torch.empty(n, dtype=torch.float64, device=ax.device)
+    l1 = torch.empty(B, dtype=torch.float64, device=ax.device)
+    sse = torch.empty(B, dtype=torch.float64, device=ax.device)
+    maxabs = torch.empty(B, dtype=torch.float32, device=ax.device)
+    check(lib.ddnm_consistency_f32(_p(ax), _p(y), m, _p(counts), _p(l1), _p(sse), _p(maxabs), _p(work), n, B, m,
+                                   _stream()), "ddnm_consistency_f32")
+    return l1, sse, maxabs

@@ -56,6 +56,9 @@ def _state_dict(path, random_from):
 
 
 def main(conf, args):
+    if str(args.get("path_y")).startswith("measurements:"):
+        raise ValueError("--path_y measurements:DIR is read by the DDNM command line (main.py, SVD path) only: the "
+                         "arbitrary-size demo degrades the picture --path_y names")
     print("Start", conf["name"])
     device = torch.device(conf.get("device") or "cuda")
     model, diffusion = create_model_and_diffusion(**select_args(conf, model_and_diffusion_defaults().keys()), conf=conf)

@@ -725,6 +725,25 @@ int ddnm_sample_stats_f32(const float* x, int64_t image_stride, int64_t sample_s
                           double* sse_mean /* [B], NULL iff x_orig NULL */, double* std_mean /* [B] */, double* work,
                           int64_t work_elems, int32_t B, int32_t K, int64_t chw, void* stream);
 
+/* Data consistency: per-row norms of the residual d = A x^ - y of B measurement rows of up to m entries.  Row b of both
+ * operands starts at b*row_stride floats (row_stride >= m) and has n_b = counts ? counts[b] : m valid entries,
+ * 0 <= n_b <= m; entries at or beyond n_b are not read (a mask bank pads its rows).  Per valid entry
+ * d = (double)ax - (double)y, which is exact; l1[b] = sum |d| and sse[b] = sum d^2 in fp64, maxabs[b] = (float)max |d|;
+ * n_b = 0 gives three zeros.  A row takes ceil(m / 2048) workgroups whatever n_b is, and their partials go to `work` and
+ * are added in an order that depends on m alone, without atomics: a row's three outputs are bit for bit the same alone
+ * and at any row of any batch.  16-byte loads where the pointers, row_stride and the position in the row allow,
+ * element-wise otherwise (same entries on the same thread in the same order: same bits).
+ * counts: int32 [B] the device can read.  Device memory is clamped to [0, m] by the kernel; pinned or managed memory,
+ * which the host can read too, is checked before the launch; pageable host memory is refused (DDNM_E_BADARG).
+ * work: ddnm_consistency_workspace_elems(B, m) doubles (= 3 * B * ceil(m / 2048)), not read after the call.
+ * NULL ax / y / l1 / sse / maxabs / work, B < 1, m < 1 or row_stride < m: DDNM_E_BADARG; work_elems below the query, a
+ * count outside [0, m] that the host can see, or more than 2^31-1 workgroups: DDNM_E_SHAPE (the query returns the same
+ * negative codes). */
+int64_t ddnm_consistency_workspace_elems(int32_t B, int64_t m);
+int ddnm_consistency_f32(const float* ax, const float* y, int64_t row_stride, const int32_t* counts /* [B] or NULL */,
+                         double* l1 /* [B] */, double* sse /* [B] */, float* maxabs /* [B] */, double* work,
+                         int64_t work_elems, int32_t B, int64_t m, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

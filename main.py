@@ -14,7 +14,9 @@ DDNM_GPUS=1 stays in this process; loader batches smaller than the rank count --
 to the ranks, larger ones are split by image and gathered); an explicit `python -m torch.distributed.run --nproc-per-node N main.py ...`
 works as before.
 
-`--path_y synthetic:N` (ours) replaces the dataset by N seeded uniform-noise images.
+`--path_y synthetic:N` (ours) replaces the dataset by N seeded uniform-noise images; `--path_y measurements:DIR` (ours)
+restores the measurements lying in DIR (the y/ folder of a run under DDNM_SAVE_Y=1, or .npy rows / pictures of one's own)
+instead of degrading a ground truth.
 """
 import argparse
 import logging
@@ -37,7 +39,7 @@ FLAGS = [
     (("--seed",), dict(type=int, default=1234, help="seed of torch / numpy / the device generator")),
     (("--exp",), dict(type=str, default="exp", help="root of the run directory (<exp>/image_samples, <exp>/datasets, <exp>/logs)")),
     (("--deg",), dict(type=str, required=True, help="degradation operator, e.g. sr_bicubic, colorization, inpainting, cs_walshhadamard, deblur_gauss")),
-    (("--path_y",), dict(type=str, required=True, help="dataset sub-folder below <exp>/datasets, or synthetic:N")),
+    (("--path_y",), dict(type=str, required=True, help="dataset sub-folder below <exp>/datasets, synthetic:N, or measurements:DIR (given measurements, no ground truth)")),
     (("--sigma_y",), dict(type=float, default=0.0, help="std of the measurement noise on the [0,1] scale (> 0 selects DDNM+)")),
     (("--eta",), dict(type=float, default=0.85, help="eta of the DDIM-style update")),
     (("--simplified",), dict(action="store_true", help="inlined A / A^+ loop of the reference (batch size 1)")),

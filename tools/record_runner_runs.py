@@ -24,7 +24,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-SWITCHES = ("DDNM_FUSE_BATCHES", "DDNM_SAMPLES", "DDNM_NOISE", "DDNM_METRICS")       # unset unless the case sets them
+SWITCHES = ("DDNM_FUSE_BATCHES", "DDNM_SAMPLES", "DDNM_NOISE", "DDNM_METRICS", "DDNM_SAVE_Y")       # unset unless the case sets them
 HEADS = ("PSNR:", "SSIM:", "Mean-of-K", "Sample PSNR:", "Std:", "Total Average", "Number of samples:",
          "Samples per image:")
 SEED = 1234
