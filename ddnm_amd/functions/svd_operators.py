@@ -32,13 +32,11 @@ has the hook too and no `Lambda` either: all its singular values are 1, so its s
 image-order pass, the two GEMMs of `A` / `A_pinv` and one scatter-add (`CS.ddnm_plus_step`, `cs_plus_coefficients`).
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
-from .. import _lib, ops
-from .._lib import check
+from .. import ops
 from ..ops import _p
 
 
@@ -67,6 +65,14 @@ def spectral_coefficients(s, a, sigma_y, sigma_t, eta):
     return 1.0, c1, c2
 
 
+def noise_coefficients(s, a, sigma_y, sigma_t, eta):
+    """(d1m, d1n, d2m, d2n) of a `Lambda_noise`: the noise factors (d1) and the eps factors (d2) on the entries measured with
+    singular value `s` (m) and on the null space (n)."""
+    _, d1m, d2m = spectral_coefficients(s, a, sigma_y, sigma_t, eta)
+    _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
+    return d1m, d1n, d2m, d2n
+
+
 def cs_plus_coefficients(a, sigma_y, sigma_t, eta):
     """The five scalars of the fused DDNM+ step of `CS` (every singular value is 1, svd_operators.py:110):
     (a*lambda, d1n, d2n, d1r - d1n, d2r - d2n) with (lambda, d1r, d2r) = spectral_coefficients(1, ...) on the measured
@@ -85,35 +91,43 @@ def _flat(vec):
 
 def _axpby(x, y, a, b):
     out = torch.empty_like(x)
-    check(_lib.lib().ddnm_axpby_f32(_p(x), _p(y), _p(out), x.numel(), a, b, ops._stream()), "ddnm_axpby_f32")
+    ops.call("ddnm_axpby_f32", _p(x), _p(y), _p(out), x.numel(), a, b)
     return out
 
 
 def _mask_mix(x, y, mask, planes_mask, plane_elems, cx_m, cx_n, cy_m=0.0, cy_n=0.0):
     out = torch.empty_like(x)
-    check(_lib.lib().ddnm_mask_mix_f32(_p(x), _p(y), _p(mask), planes_mask, plane_elems, _p(out), x.numel(), cx_m, cx_n,
-                                       cy_m, cy_n, ops._stream()), "ddnm_mask_mix_f32")
+    ops.call("ddnm_mask_mix_f32", _p(x), _p(y), _p(mask), planes_mask, plane_elems, _p(out), x.numel(), cx_m, cx_n, cy_m, cy_n)
     return out
+
+
+def _mul_planes(x, gain, planes_gain, plane_elems):
+    """x *= gain in place, `gain` holding `planes_gain` planes of `plane_elems` entries that repeat over the planes of x."""
+    ops.call("ddnm_mul_planes_f32", _p(x), _p(gain), planes_gain, plane_elems, _p(x), x.numel())
+    return x
+
+
+def _mask_lambda(vec, epsilon, mask, planes_mask, plane_elems, a, sigma_y, sigma_t, eta):
+    """`Lambda` (epsilon None) / `Lambda_noise` of the mask-type operators: singular value 1 where `mask` is 1, null space
+    where it is 0 (svd_operators.py:361-439)."""
+    if epsilon is None:
+        lam = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)[0]
+        return _mask_mix(_flat(vec), None, mask, planes_mask, plane_elems, lam, 1.0)
+    coef = noise_coefficients(1.0, a, sigma_y, sigma_t, eta)
+    return _mask_mix(_flat(vec), _flat(epsilon), mask, planes_mask, plane_elems, *coef)
 
 
 def _site_spectral(x, y, V, n, mode, r, B, C, H, W, op, c0, c1=0.0, c2=0.0, c3=0.0):
     out = torch.empty_like(x)
-    check(_lib.lib().ddnm_site_spectral_f32(_p(x), _p(y), _p(V), n, mode, r, B, C, H, W, _p(out), op, c0, c1, c2, c3,
-                                            ops._stream()), "ddnm_site_spectral_f32")
+    ops.call("ddnm_site_spectral_f32", _p(x), _p(y), _p(V), n, mode, r, B, C, H, W, _p(out), op, c0, c1, c2, c3)
     return out
 
 
 def _row_svd(row, device):
-    """sigma and V of a 1 x n measurement row via torch.svd on the host, like the reference's constructors
+    """sigma, V and U[0, 0] (= +-1) of a 1 x n measurement row via torch.svd on the host, like the reference's constructors
     (svd_operators.py:487,633); the null-space columns of V are LAPACK's choice and are part of the contract."""
     U, S, V = torch.svd(torch.tensor([row], dtype=torch.float32), some=False)
-    return float(S[0]), V.contiguous().to(device)
-
-
-def _row_svd_u(row):
-    """U_small[0, 0] (= +-1) of the same decomposition (U / Ut of SuperResolution and Colorization, :519-523,658-662)."""
-    U, _, _ = torch.svd(torch.tensor([row], dtype=torch.float32), some=False)
-    return float(U[0, 0])
+    return float(S[0]), V.contiguous().to(device), float(U[0, 0])
 
 
 def _gather(vec, idx, n_out, scale=None):
@@ -121,8 +135,7 @@ def _gather(vec, idx, n_out, scale=None):
     v = _flat(vec)
     B, n_in = v.shape
     out = torch.empty(B, n_out, dtype=torch.float32, device=v.device)
-    check(_lib.lib().ddnm_gather_scale_f32(_p(v), _p(idx), _p(scale), _p(out), B, n_in, n_out, ops._stream()),
-          "ddnm_gather_scale_f32")
+    ops.call("ddnm_gather_scale_f32", _p(v), _p(idx), _p(scale), _p(out), B, n_in, n_out)
     return out
 
 
@@ -140,9 +153,44 @@ def _site_matmul(vec, M, sites, n, sb, ss, sj, trans):
         # Mop = M (trans 0): out = in . M^T -> B operand stored [N = i][K = j] = M itself; Mop = M^T: stored [K = j][N = i]
         ops.bgemm(v, M, out, rows, n, n, lda=n, ldb=n, ldc=n, transb=not trans)
         return out
-    check(_lib.lib().ddnm_site_matmul_f32(_p(v), _p(M), _p(out), v.shape[0], sites, n, sb, ss, sj, int(trans),
-                                          ops._stream()), "ddnm_site_matmul_f32")
+    ops.call("ddnm_site_matmul_f32", _p(v), _p(M), _p(out), v.shape[0], sites, n, sb, ss, sj, int(trans))
     return out
+
+
+def _left(L, x, rows, inner, planes, out=None, images=None):
+    """out[p] = L . X[p] for the `planes` planes X [inner x inner] of `x`; L is [rows x inner].  `images` = (C, batch stride):
+    `x` is [B][C] planes read through its batch stride (et as the [:, :3] view of a 6-channel output)."""
+    if out is None:
+        out = torch.empty(planes, rows, inner, dtype=torch.float32, device=x.device)
+    C, sb = images or (1, 0)
+    return ops.bgemm(L, x, out, rows, inner, inner, lda=inner, ldb=inner, ldc=inner, transb=False, batch=planes, inner=C,
+                     sB=(sb, inner * inner) if images else (inner * inner, 0),
+                     sC=(C * rows * inner, rows * inner) if images else (rows * inner, 0))
+
+
+def _right(t, Rt, rows, inner, cols, planes, out=None, ldc=None, D=None, beta=None):
+    """out[p] = T[p] . R for the `planes` planes T [rows x inner] of `t`; R is given transposed, Rt [cols x inner] row-major
+    (the [N][K] operand layout of the GEMM).  `out` with its own leading dimension `ldc`: the product lands in the top-left
+    rows x cols of wider planes.  `beta`: the epilogue out += beta * D[p], D [rows x cols] per plane (D may be None)."""
+    if out is None:
+        out = torch.empty(planes, rows, cols, dtype=torch.float32, device=t.device)
+    ldd, sD = (0, 0) if beta is None else (cols, rows * cols)
+    return ops.bgemm(t, Rt, out, rows, cols, inner, lda=inner, ldb=inner, ldc=ldc or cols, transb=True, batch=planes,
+                     sA=(rows * inner, 0), sC=(out.numel() // planes, 0), D=D, ldd=ldd, sD=(sD, 0), beta=beta or 0.0)
+
+
+def _two_sided(L, x, Rt, rows, inner, cols, **right):
+    """L . X . R for every (image, channel) plane X [inner x inner] of `x`, as [planes, rows, cols] (see _left / _right)."""
+    planes = x.numel() // (inner * inner)
+    return _right(_left(L, x, rows, inner, planes), Rt, rows, inner, cols, planes, **right)
+
+
+def _plus_state(op, B):
+    """What begin_plus_run(y) left for a batch of B images (`op._plus_run` behind its batch size)."""
+    run = getattr(op, "_plus_run", None)
+    if run is None or run[0] != B:
+        raise RuntimeError("ddnm_plus_step needs begin_plus_run(y) for this batch first")
+    return run[1:]
 
 
 def _pad_scale(f, n):
@@ -225,7 +273,6 @@ class A_functions:
     # ---- engine hook -----------------------------------------------------------------
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         """Generic step: x0, proj = A^+(A x0 - y), combine.  Subclasses fuse it."""
-        B = xt.shape[0]
         ops.step_x0(xt, et, s, out=x0_out)
         resid = _axpby(self.A(x0_out), _flat(y), 1.0, -1.0)
         proj = self.A_pinv(resid).reshape(xt.shape)
@@ -268,13 +315,39 @@ class Denoising(A_functions):
 
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         B = xt.shape[0]
-        ep, es = ops._et_args(et)
-        fn, nz = ops.step_noise_args("ddnm_step_denoise_f32", noise, xt)
-        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(x0_out), _p(xt_next), B, xt.numel() // B,
-                                      ctypes.byref(s), ops._stream()), fn)
+        ops.step_call("ddnm_step_denoise_f32", xt, et, noise, y, _p(x0_out), _p(xt_next), B, xt.numel() // B, s)
 
 
-class SuperResolution(A_functions):
+class _RowOperator(A_functions):
+    """What SuperResolution and Colorization share: every site (r x r patch / pixel) is measured by the same 1 x n row
+    `_row()`, decomposed once on the host; `_site(v)` = (n, mode, r, B, C, H, W) of ddnm_site_spectral_f32."""
+
+    def _svd(self):
+        if not hasattr(self, "_V"):
+            self._s, self._V, self._u = _row_svd(self._row(), self.device)
+        return self._s, self._V
+
+    def U(self, vec):                                                      # svd_operators.py:519-523,658-662 (U is 1 x 1)
+        self._svd()
+        return _axpby(_flat(vec), None, self._u, 0.0)
+
+    Ut = U
+
+    def add_zeros(self, vec):                                              # :528-533,667-671
+        return _gather(vec, None, self._spectral_dim())
+
+    def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:535-571,669-695
+        s, V = self._svd()
+        v = _flat(vec)
+        return _site_spectral(v, None, V, *self._site(v), 0, spectral_coefficients(s, a, sigma_y, sigma_t, eta)[0])
+
+    def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :573-623,697-736
+        s, V = self._svd()
+        v = _flat(vec)
+        return _site_spectral(v, _flat(epsilon), V, *self._site(v), 1, *noise_coefficients(s, a, sigma_y, sigma_t, eta))
+
+
+class SuperResolution(_RowOperator):
     def __init__(self, channels, img_dim, ratio, device):
         assert img_dim % ratio == 0
         self.channels, self.img_dim, self.ratio, self.device = channels, img_dim, ratio, device
@@ -290,25 +363,24 @@ class SuperResolution(A_functions):
         x = _img(vec, self.channels, self.img_dim)
         B = x.shape[0]
         y = torch.empty(B, self.channels * self.y_dim ** 2, dtype=torch.float32, device=x.device)
-        check(_lib.lib().ddnm_op_avgpool_f32(_p(x), _p(y), B * self.channels, self.img_dim, self.img_dim, self.ratio,
-                                             ops._stream()), "ddnm_op_avgpool_f32")
+        ops.call("ddnm_op_avgpool_f32", _p(x), _p(y), B * self.channels, self.img_dim, self.img_dim, self.ratio)
         return y
 
     def A_pinv(self, vec):
         B = vec.shape[0]
         y = vec.reshape(B, -1).float().contiguous()
         x = torch.empty(B, self.channels * self.img_dim ** 2, dtype=torch.float32, device=y.device)
-        check(_lib.lib().ddnm_op_upsample_f32(_p(y), _p(x), B * self.channels, self.img_dim, self.img_dim, self.ratio,
-                                              ops._stream()), "ddnm_op_upsample_f32")
+        ops.call("ddnm_op_upsample_f32", _p(y), _p(x), B * self.channels, self.img_dim, self.img_dim, self.ratio)
         return x
 
     def singulars(self):
         return torch.full((self.channels * self.y_dim ** 2,), 1.0 / self.ratio, device=self.device)
 
-    def _svd(self):
-        if not hasattr(self, "_V"):
-            self._s, self._V = _row_svd([1 / self.ratio ** 2] * self.ratio ** 2, self.device)
-        return self._s, self._V
+    def _row(self):
+        return [1 / self.ratio ** 2] * self.ratio ** 2
+
+    def _site(self, v):
+        return self.ratio ** 2, 0, self.ratio, v.shape[0], self.channels, self.img_dim, self.img_dim
 
     def _tables(self):
         """Index tables of V / Vt (svd_operators.py:490-517): image (CHW) <-> site-major patches [C*y*y][r*r]
@@ -341,40 +413,16 @@ class SuperResolution(A_functions):
         t = _site_matmul(t, self._svd()[1], N // n, n, N, n, 1, trans=False)
         return _gather(t, site2img, N)
 
-    def U(self, vec):                                                      # :519-523 (U is 1 x 1)
-        return _axpby(_flat(vec), None, _row_svd_u([1 / self.ratio ** 2] * self.ratio ** 2), 0.0)
-
-    Ut = U
-
-    def add_zeros(self, vec):                                              # :528-533
-        return _gather(vec, None, self._spectral_dim())
-
-    def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:535-571
-        s, V = self._svd()
-        lam = spectral_coefficients(s, a, sigma_y, sigma_t, eta)[0]
-        v = _flat(vec)
-        return _site_spectral(v, None, V, self.ratio ** 2, 0, self.ratio, v.shape[0], self.channels, self.img_dim,
-                              self.img_dim, 0, lam)
-
-    def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :573-623
-        s, V = self._svd()
-        _, d1m, d2m = spectral_coefficients(s, a, sigma_y, sigma_t, eta)
-        _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
-        v = _flat(vec)
-        return _site_spectral(v, _flat(epsilon), V, self.ratio ** 2, 0, self.ratio, v.shape[0], self.channels,
-                              self.img_dim, self.img_dim, 1, d1m, d1n, d2m, d2n)
-
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         if self.ratio != 4 or self.channels != 3:
             return super().ddnm_step(xt, et, noise, y, s, x0_out, xt_next)
-        B = xt.shape[0]
-        ep, es = ops._et_args(et)
-        fn, nz = ops.step_noise_args("ddnm_step_sr_avgpool_f32", noise, xt)
-        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(x0_out), _p(xt_next), B, self.img_dim, self.img_dim,
-                                      self.ratio, ctypes.byref(s), ops._stream()), fn)
+        ops.step_call("ddnm_step_sr_avgpool_f32", xt, et, noise, y, _p(x0_out), _p(xt_next), xt.shape[0], self.img_dim,
+                      self.img_dim, self.ratio, s)
 
 
-class Colorization(A_functions):
+class Colorization(_RowOperator):
+    THIRDS = (0.3333, 0.3334, 0.3333)       # the default measurement row (svd_operators.py:632)
+
     def __init__(self, img_dim, device, weights=None):
         """`weights`: per-pixel measurement row; None = (0.3333, 0.3334, 0.3333) (svd_operators.py:632).
         The simplified path passes (1/3, 1/3, 1/3) (guided_diffusion/diffusion.py:33-42)."""
@@ -391,28 +439,25 @@ class Colorization(A_functions):
         x = _img(vec, 3, self.img_dim)
         B, HW = x.shape[0], self.img_dim ** 2
         y = torch.empty(B, HW, dtype=torch.float32, device=x.device)
-        check(_lib.lib().ddnm_op_color_A_f32(_p(x), _p(y), B, HW, self._w, ops._stream()), "ddnm_op_color_A_f32")
+        ops.call("ddnm_op_color_A_f32", _p(x), _p(y), B, HW, self._w)
         return y
 
     def A_pinv(self, vec):
         B, HW = vec.shape[0], self.img_dim ** 2
         y = vec.reshape(B, -1).float().contiguous()
         x = torch.empty(B, 3 * HW, dtype=torch.float32, device=y.device)
-        check(_lib.lib().ddnm_op_color_pinv_f32(_p(y), _p(x), B, HW, self._w, ops._stream()), "ddnm_op_color_pinv_f32")
+        ops.call("ddnm_op_color_pinv_f32", _p(y), _p(x), B, HW, self._w)
         return x
 
     def singulars(self):
-        w = torch.tensor([0.3333, 0.3334, 0.3333] if self._w is None else list(self._w))
+        w = torch.tensor(self._row())
         return torch.full((self.img_dim ** 2,), float((w * w).sum().sqrt()), device=self.device)
 
-    def _svd(self):
-        if not hasattr(self, "_V"):
-            row = [0.3333, 0.3334, 0.3333] if self._w is None else [float(v) for v in self._w]
-            self._s, self._V = _row_svd(row, self.device)
-        return self._s, self._V
-
     def _row(self):
-        return [0.3333, 0.3334, 0.3333] if self._w is None else [float(v) for v in self._w]
+        return list(self.THIRDS) if self._w is None else [float(v) for v in self._w]
+
+    def _site(self, v):
+        return 3, 1, 1, v.shape[0], 3, self.img_dim, self.img_dim
 
     def Vt(self, vec):                                                     # svd_operators.py:647-656
         hw = self.img_dim ** 2                  # needles of the CHW planes; the spectral order is component-major too
@@ -422,34 +467,9 @@ class Colorization(A_functions):
         hw = self.img_dim ** 2
         return _site_matmul(vec, self._svd()[1], hw, 3, 3 * hw, 1, hw, trans=False)
 
-    def U(self, vec):                                                      # :658-662
-        return _axpby(_flat(vec), None, _row_svd_u(self._row()), 0.0)
-
-    Ut = U
-
-    def add_zeros(self, vec):                                              # :667-671
-        return _gather(vec, None, self._spectral_dim())
-
-    def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:669-695
-        s, V = self._svd()
-        lam = spectral_coefficients(s, a, sigma_y, sigma_t, eta)[0]
-        v = _flat(vec)
-        return _site_spectral(v, None, V, 3, 1, 1, v.shape[0], 3, self.img_dim, self.img_dim, 0, lam)
-
-    def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :697-736
-        s, V = self._svd()
-        _, d1m, d2m = spectral_coefficients(s, a, sigma_y, sigma_t, eta)
-        _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
-        v = _flat(vec)
-        return _site_spectral(v, _flat(epsilon), V, 3, 1, 1, v.shape[0], 3, self.img_dim, self.img_dim, 1, d1m, d1n,
-                              d2m, d2n)
-
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
-        B = xt.shape[0]
-        ep, es = ops._et_args(et)
-        fn, nz = ops.step_noise_args("ddnm_step_color_f32", noise, xt)
-        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(x0_out), _p(xt_next), B, self.img_dim ** 2, self._w,
-                                      ctypes.byref(s), ops._stream()), fn)
+        ops.step_call("ddnm_step_color_f32", xt, et, noise, y, _p(x0_out), _p(xt_next), xt.shape[0], self.img_dim ** 2,
+                      self._w, s)
 
 
 def _rank_table(keep):
@@ -489,16 +509,14 @@ class Inpainting(A_functions):
         x = _img(vec, 3, self.img_dim)
         B = x.shape[0]
         y = torch.empty(B, 3 * self.n_kept, dtype=torch.float32, device=x.device)
-        check(_lib.lib().ddnm_op_inpaint_A_f32(_p(x), _p(self.rank), self.n_kept, _p(y), B, self.img_dim ** 2,
-                                               ops._stream()), "ddnm_op_inpaint_A_f32")
+        ops.call("ddnm_op_inpaint_A_f32", _p(x), _p(self.rank), self.n_kept, _p(y), B, self.img_dim ** 2)
         return y
 
     def A_pinv(self, vec):
         B = vec.shape[0]
         y = vec.reshape(B, -1).float().contiguous()
         x = torch.empty(B, 3 * self.img_dim ** 2, dtype=torch.float32, device=y.device)
-        check(_lib.lib().ddnm_op_inpaint_pinv_f32(_p(y), _p(self.rank), self.n_kept, _p(x), B, self.img_dim ** 2,
-                                                  ops._stream()), "ddnm_op_inpaint_pinv_f32")
+        ops.call("ddnm_op_inpaint_pinv_f32", _p(y), _p(self.rank), self.n_kept, _p(x), B, self.img_dim ** 2)
         return x
 
     def singulars(self):
@@ -532,20 +550,14 @@ class Inpainting(A_functions):
         return _gather(vec, None, self._spectral_dim())
 
     def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:361-387
-        lam = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)[0]
-        return _mask_mix(_flat(vec), None, self.kept_mask, 1, self.img_dim ** 2, lam, 1.0)
+        return _mask_lambda(vec, None, self.kept_mask, 1, self.img_dim ** 2, a, sigma_y, sigma_t, eta)
 
     def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :389-439
-        _, d1m, d2m = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)
-        _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
-        return _mask_mix(_flat(vec), _flat(epsilon), self.kept_mask, 1, self.img_dim ** 2, d1m, d1n, d2m, d2n)
+        return _mask_lambda(vec, epsilon, self.kept_mask, 1, self.img_dim ** 2, a, sigma_y, sigma_t, eta)
 
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
-        B = xt.shape[0]
-        ep, es = ops._et_args(et)
-        fn, nz = ops.step_noise_args("ddnm_step_inpaint_f32", noise, xt)
-        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), _p(self.rank), self.n_kept, _p(x0_out), _p(xt_next), B,
-                                      self.img_dim ** 2, ctypes.byref(s), ops._stream()), fn)
+        ops.step_call("ddnm_step_inpaint_f32", xt, et, noise, y, _p(self.rank), self.n_kept, _p(x0_out), _p(xt_next),
+                      xt.shape[0], self.img_dim ** 2, s)
 
 
 class InpaintingBank:
@@ -642,8 +654,7 @@ class PerImageInpainting(A_functions):
         B = x.shape[0]
         self._check_batch(B)
         y = ops.fill_(torch.empty(B, self.y_dim, dtype=torch.float32, device=x.device))      # padding is exactly 0
-        check(_lib.lib().ddnm_op_inpaint_A_pi_f32(_p(x), _p(self.rank), max(self.n_kept), _p(y), self.y_dim, B,
-                                                  self.img_dim ** 2, ops._stream()), "ddnm_op_inpaint_A_pi_f32")
+        ops.call("ddnm_op_inpaint_A_pi_f32", _p(x), _p(self.rank), max(self.n_kept), _p(y), self.y_dim, B, self.img_dim ** 2)
         return y
 
     def A_pinv(self, vec):
@@ -653,8 +664,7 @@ class PerImageInpainting(A_functions):
         if y.shape[1] != self.y_dim:
             raise ValueError(f"measurement rows have {y.shape[1]} entries, the bank's y_dim is {self.y_dim}")
         x = torch.empty(B, 3 * self.img_dim ** 2, dtype=torch.float32, device=y.device)
-        check(_lib.lib().ddnm_op_inpaint_pinv_pi_f32(_p(y), self.y_dim, _p(self.rank), max(self.n_kept), _p(x), B,
-                                                     self.img_dim ** 2, ops._stream()), "ddnm_op_inpaint_pinv_pi_f32")
+        ops.call("ddnm_op_inpaint_pinv_pi_f32", _p(y), self.y_dim, _p(self.rank), max(self.n_kept), _p(x), B, self.img_dim ** 2)
         return x
 
     def _ragged(self, *args, **kwargs):
@@ -665,24 +675,19 @@ class PerImageInpainting(A_functions):
 
     def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # Inpainting.Lambda with image b's mask
         self._check_batch(vec.shape[0])
-        lam = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)[0]
-        return _mask_mix(_flat(vec), None, self.kept3, 3 * len(self), self.img_dim ** 2, lam, 1.0)
+        return _mask_lambda(vec, None, self.kept3, 3 * len(self), self.img_dim ** 2, a, sigma_y, sigma_t, eta)
 
     def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):
         self._check_batch(vec.shape[0])
-        _, d1m, d2m = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)
-        _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
-        return _mask_mix(_flat(vec), _flat(epsilon), self.kept3, 3 * len(self), self.img_dim ** 2, d1m, d1n, d2m, d2n)
+        return _mask_lambda(vec, epsilon, self.kept3, 3 * len(self), self.img_dim ** 2, a, sigma_y, sigma_t, eta)
 
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         B = xt.shape[0]
         self._check_batch(B)
         if y.shape[0] != B or y.numel() != B * self.y_dim:
             raise ValueError(f"y must be [{B}, {self.y_dim}], got {tuple(y.shape)}")
-        ep, es = ops._et_args(et)
-        fn, nz = ops.step_noise_args("ddnm_step_inpaint_pi_f32", noise, xt)
-        check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), self.y_dim, _p(self.rank), max(self.n_kept), _p(x0_out),
-                                      _p(xt_next), B, self.img_dim ** 2, ctypes.byref(s), ops._stream()), fn)
+        ops.step_call("ddnm_step_inpaint_pi_f32", xt, et, noise, y, self.y_dim, _p(self.rank), max(self.n_kept), _p(x0_out),
+                      _p(xt_next), B, self.img_dim ** 2, s)
 
 
 class WalshHadamardCS(A_functions):
@@ -710,48 +715,42 @@ class WalshHadamardCS(A_functions):
     def measurement_size(self):
         return self.n_keep
 
-    def A(self, vec):
+    def _fwht(self, planes):
+        out = torch.empty_like(planes)
+        B = planes.numel() // (self.channels * self.N)
+        ops.call("ddnm_fwht2d_f32", _p(planes), _p(out), B * self.channels, self.img_dim)
+        return out
+
+    def _permuted(self, vec, n):
+        """The first `n` entries of the permuted, (k, c)-interleaved order of the coefficient planes of `vec`, as [B, n]."""
         x = _img(vec, self.channels, self.img_dim)
-        B = x.shape[0]
-        coef = torch.empty_like(x)
-        L = _lib.lib()
-        check(L.ddnm_fwht2d_f32(_p(x), _p(coef), B * self.channels, self.img_dim, ops._stream()), "ddnm_fwht2d_f32")
-        y = torch.empty(B, self.n_keep, dtype=torch.float32, device=x.device)
-        check(L.ddnm_wh_gather_f32(_p(coef), _p(self.perm), _p(y), B, self.channels, self.N, self.n_keep,
-                                   ops._stream()), "ddnm_wh_gather_f32")
-        return y
+        coef = self._fwht(x)                    # held in a local across the launch that reads it
+        out = torch.empty(x.shape[0], n, dtype=torch.float32, device=x.device)
+        ops.call("ddnm_wh_gather_f32", _p(coef), _p(self.perm), _p(out), x.shape[0], self.channels, self.N, n)
+        return out
+
+    def _unpermuted(self, vec, n):
+        """Inverse of `_permuted`: [B, n] (entries beyond n are zero) -> the image, as [B, C * N]."""
+        z = _flat(vec)
+        B = z.shape[0]
+        planes = torch.empty(B, self.channels, self.N, dtype=torch.float32, device=z.device)
+        ops.call("ddnm_wh_scatter_f32", _p(z), _p(self.perm), _p(planes), B, self.channels, self.N, n)
+        return self._fwht(planes).reshape(B, -1)
+
+    def A(self, vec):
+        return self._permuted(vec, self.n_keep)
 
     def A_pinv(self, vec):
-        B = vec.shape[0]
-        y = vec.reshape(B, -1).float().contiguous()
-        planes = torch.empty(B, self.channels, self.N, dtype=torch.float32, device=y.device)
-        L = _lib.lib()
-        check(L.ddnm_wh_scatter_f32(_p(y), _p(self.perm), _p(planes), B, self.channels, self.N, self.n_keep,
-                                    ops._stream()), "ddnm_wh_scatter_f32")
-        out = torch.empty_like(planes)
-        check(L.ddnm_fwht2d_f32(_p(planes), _p(out), B * self.channels, self.img_dim, ops._stream()),
-              "ddnm_fwht2d_f32")
-        return out.reshape(B, -1)
+        return self._unpermuted(vec, self.n_keep)
 
     def singulars(self):
         return torch.ones(self.n_keep, device=self.device)
 
     def Vt(self, vec):                                                     # svd_operators.py:236-237: fwht, permute, (k, c) interleave
-        x = _img(vec, self.channels, self.img_dim)
-        B = x.shape[0]
-        coef = self._fwht(x)
-        z = torch.empty(B, self.channels * self.N, dtype=torch.float32, device=x.device)
-        check(_lib.lib().ddnm_wh_gather_f32(_p(coef), _p(self.perm), _p(z), B, self.channels, self.N,
-                                            self.channels * self.N, ops._stream()), "ddnm_wh_gather_f32")
-        return z
+        return self._permuted(vec, self.channels * self.N)
 
     def V(self, vec):                                                      # :231-234
-        z = _flat(vec)
-        B = z.shape[0]
-        planes = torch.empty(B, self.channels, self.N, dtype=torch.float32, device=z.device)
-        check(_lib.lib().ddnm_wh_scatter_f32(_p(z), _p(self.perm), _p(planes), B, self.channels, self.N,
-                                             self.channels * self.N, ops._stream()), "ddnm_wh_scatter_f32")
-        return self._fwht(planes).reshape(B, -1)
+        return self._unpermuted(vec, self.channels * self.N)
 
     def U(self, vec):                                                      # :239-243
         return _flat(vec).clone()
@@ -761,24 +760,12 @@ class WalshHadamardCS(A_functions):
     def add_zeros(self, vec):                                              # :248-251
         return _gather(vec, None, self._spectral_dim())
 
-    def _fwht(self, planes):
-        out = torch.empty_like(planes)
-        B = planes.numel() // (self.channels * self.N)
-        check(_lib.lib().ddnm_fwht2d_f32(_p(planes), _p(out), B * self.channels, self.img_dim, ops._stream()),
-              "ddnm_fwht2d_f32")
-        return out
-
     def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:253-279
-        lam = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)[0]
         coef = self._fwht(_flat(vec))
-        coef = _mask_mix(coef, None, self.mask, self.channels, self.N, lam, 1.0)
-        return self._fwht(coef)
+        return self._fwht(_mask_lambda(coef, None, self.mask, self.channels, self.N, a, sigma_y, sigma_t, eta))
 
     def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :281-320 (no forward transform there)
-        _, d1m, d2m = spectral_coefficients(1.0, a, sigma_y, sigma_t, eta)
-        _, d1n, d2n = spectral_coefficients(0.0, a, sigma_y, sigma_t, eta)
-        mixed = _mask_mix(_flat(vec), _flat(epsilon), self.mask, self.channels, self.N, d1m, d1n, d2m, d2n)
-        return self._fwht(mixed)
+        return self._fwht(_mask_lambda(vec, epsilon, self.mask, self.channels, self.N, a, sigma_y, sigma_t, eta))
 
     def begin_run(self, y):
         """Called by the reverse loop once per run: A^+ y is constant over the run and is evaluated here.  (It used to
@@ -795,9 +782,8 @@ class WalshHadamardCS(A_functions):
         self._apy = self._apy.reshape(xt.shape)
         ops.step_x0(xt, et, s, out=x0_out)
         proj = torch.empty_like(xt)
-        check(_lib.lib().ddnm_fwht2d_masked_f32(_p(x0_out), _p(self.mask), self.channels, _p(proj),
-                                                B * self.channels, self.img_dim, _p(self._buf(B)), ops._stream()),
-              "ddnm_fwht2d_masked_f32")
+        ops.call("ddnm_fwht2d_masked_f32", _p(x0_out), _p(self.mask), self.channels, _p(proj), B * self.channels, self.img_dim,
+                 _p(self._buf(B)))
         ops.step_combine(x0_out, proj, self._apy, noise, et, s, out=xt_next)
 
 
@@ -830,26 +816,29 @@ class CS(A_functions):
     def measurement_size(self):
         return self.channels * self.y_dim ** 2 * self.cs_size
 
+    def _measure(self, P, T):
+        """T [patches, cs] = P [patches, 1024] . M^T: the measured coefficients of every patch, (c, patch, k) order (:143)."""
+        ps2, cs = self.ratio ** 2, self.cs_size
+        return ops.bgemm(P, self.M, T, P.numel() // ps2, cs, ps2, lda=ps2, ldb=ps2, ldc=cs, transb=True)
+
+    def _expand(self, T, P):
+        """P [patches, 1024] = T [patches, cs] . M: back from the measured subspace."""
+        ps2, cs = self.ratio ** 2, self.cs_size
+        return ops.bgemm(T, self.M, P, P.numel() // ps2, ps2, cs, lda=cs, ldb=ps2, ldc=ps2, transb=False)
+
     def A(self, vec):
         x = _img(vec, self.channels, self.img_dim)
-        B, ps2, cs = x.shape[0], self.ratio ** 2, self.cs_size
-        npatch = self._npatch(B)
-        P = torch.empty(npatch, ps2, dtype=torch.float32, device=x.device)
-        check(_lib.lib().ddnm_patchify_f32(_p(x), _p(P), B * self.channels, self.img_dim, self.ratio, 0, ops._stream()),
-              "ddnm_patchify_f32")
-        y = torch.empty(B, self.channels * self.y_dim ** 2 * cs, dtype=torch.float32, device=x.device)
-        ops.bgemm(P, self.M, y, npatch, cs, ps2, lda=ps2, ldb=ps2, ldc=cs, transb=True)      # (c, patch, k) order, :143
-        return y
+        B = x.shape[0]
+        P = torch.empty(self._npatch(B), self.ratio ** 2, dtype=torch.float32, device=x.device)
+        ops.call("ddnm_patchify_f32", _p(x), _p(P), B * self.channels, self.img_dim, self.ratio, 0)
+        return self._measure(P, torch.empty(B, self.measurement_size(), dtype=torch.float32, device=x.device))
 
     def A_pinv(self, vec):
-        B, ps2, cs = vec.shape[0], self.ratio ** 2, self.cs_size
-        y = vec.reshape(B, -1).float().contiguous()
-        npatch = self._npatch(B)
-        P = torch.empty(npatch, ps2, dtype=torch.float32, device=y.device)
-        ops.bgemm(y, self.M, P, npatch, ps2, cs, lda=cs, ldb=ps2, ldc=ps2, transb=False)
+        y = _flat(vec)
+        B = y.shape[0]
+        P = self._expand(y, torch.empty(self._npatch(B), self.ratio ** 2, dtype=torch.float32, device=y.device))
         x = torch.empty(B, self.channels * self.img_dim ** 2, dtype=torch.float32, device=y.device)
-        check(_lib.lib().ddnm_patchify_f32(_p(P), _p(x), B * self.channels, self.img_dim, self.ratio, 1, ops._stream()),
-              "ddnm_patchify_f32")
+        ops.call("ddnm_patchify_f32", _p(P), _p(x), B * self.channels, self.img_dim, self.ratio, 1)
         return x
 
     def singulars(self):
@@ -878,17 +867,10 @@ class CS(A_functions):
         """One DDNM+ reverse step: x0|t into `x0_out` (uncorrected, as the loop returns and time-travels from it), x_{t-1}
         into `xt_next`.  `et` may be the [:, :3] view of a 6-channel network output (read through its strides).  Four
         launches: pre kernel, T = w M^T, P = T M (into w's buffer), post kernel."""
-        run = getattr(self, "_plus_run", None)
-        B = xt.shape[0]
-        if run is None or run[0] != B:
-            raise RuntimeError("ddnm_plus_step needs begin_plus_run(y) for this batch first")
-        _, aty, w, T = run
-        ps, ps2, cs, npatch = self.ratio, self.ratio ** 2, self.cs_size, self._npatch(B)
+        aty, w, T = _plus_state(self, xt.shape[0])
         coef = cs_plus_coefficients(s.sqrt_at_next, sigma_y, sigma_t, eta)
-        ops.step_plus_cs_pre(xt, et, noise, aty, s, coef, x0_out, xt_next, w, ps)
-        ops.bgemm(w, self.M, T, npatch, cs, ps2, lda=ps2, ldb=ps2, ldc=cs, transb=True)
-        ops.bgemm(T, self.M, w, npatch, ps2, cs, lda=cs, ldb=ps2, ldc=ps2, transb=False)
-        ops.step_plus_cs_post(w, xt_next, ps)
+        ops.step_plus_cs_pre(xt, et, noise, aty, s, coef, x0_out, xt_next, w, self.ratio)
+        ops.step_plus_cs_post(self._expand(self._measure(w, T), w), xt_next, self.ratio)
 
 
 class PixelMask(A_functions):
@@ -1031,38 +1013,31 @@ class _SpectralPlus:
         if y.shape[1] != C * m * m:
             raise ValueError(f"measurement rows have {y.shape[1]} entries, expected {C} x {m} x {m}")
         bc = B * C
-        t = torch.empty(bc, m, m, dtype=torch.float32, device=y.device)
-        ops.bgemm(f["Ult"], y, t, m, m, m, lda=m, ldb=m, ldc=m, transb=False, batch=bc, sB=(m * m, 0), sC=(m * m, 0))
+        t = _left(f["Ult"], y, m, m, bc)
         y_hat = ops.fill_(torch.empty(B, C, d, d, dtype=torch.float32, device=y.device))
         # (Ul^T Y) Ur into the top-left m x m of each zeroed d x d plane (ldc = d), then g^+
-        ops.bgemm(t, f["Urt"], y_hat, m, m, m, lda=m, ldb=m, ldc=d, transb=True, batch=bc, sA=(m * m, 0), sC=(d * d, 0))
-        check(_lib.lib().ddnm_mul_planes_f32(_p(y_hat), _p(f["ginv"]), f["ginv"].shape[0], d * d, _p(y_hat),
-                                             y_hat.numel(), ops._stream()), "ddnm_mul_planes_f32")
+        _right(t, f["Urt"], m, m, m, bc, out=y_hat, ldc=d)
+        _mul_planes(y_hat, f["ginv"], f["ginv"].shape[0], d * d)
         self._plus_run = (B, y_hat, torch.empty(2, bc, d, d, dtype=torch.float32, device=y.device),
                           torch.empty(2, B, C, d, d, dtype=torch.float32, device=y.device))
 
     def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
         """One DDNM+ reverse step: x0|t into `x0_out` (uncorrected, as the loop returns and time-travels from it), x_{t-1}
         into `xt_next`.  `et` may be the [:, :3] view of a 6-channel network output (read through its strides)."""
-        run = getattr(self, "_plus_run", None)
         B = xt.shape[0]
-        if run is None or run[0] != B:
-            raise RuntimeError("ddnm_plus_step needs begin_plus_run(y) for this batch first")
-        _, y_hat, t1, hat = run
+        y_hat, t1, hat = _plus_state(self, B)
         f = self._plus_factors()
         C, d = self.channels, self.img_dim
-        bc, dd = B * C, d * d
+        bc = B * C
         ops.step_x0(xt, et, s, out=x0_out)                 # validates et's layout too
         # x^_t = Vl^T X_t Vr and e^ = Vl^T E Vr: left products per tensor, the right product over all 2 B C planes
-        ops.bgemm(f["Vlt"], xt, t1[0], d, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, sB=(dd, 0), sC=(dd, 0))
-        ops.bgemm(f["Vlt"], et, t1[1], d, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, inner=C,
-                  sB=(et.stride(0), dd), sC=(C * dd, dd))
-        ops.bgemm(t1, f["Vrt"], hat, d, d, d, lda=d, ldb=d, ldc=d, transb=True, batch=2 * bc, sA=(dd, 0), sC=(dd, 0))
+        _left(f["Vlt"], xt, d, d, bc, out=t1[0])
+        _left(f["Vlt"], et, d, d, bc, out=t1[1], images=(C, et.stride(0)))
+        _right(t1, f["Vrt"], d, d, d, 2 * bc, out=hat)
         g = f["gains"]
-        ops.step_plus_spectral(hat[0], hat[1], y_hat, g, dd if g.shape[0] > 1 else 0, noise, s, sigma_y, sigma_t, eta,
+        ops.step_plus_spectral(hat[0], hat[1], y_hat, g, d * d if g.shape[0] > 1 else 0, noise, s, sigma_y, sigma_t, eta,
                                out=hat[0])
-        ops.bgemm(f["Vl"], hat[0], t1[0], d, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, sB=(dd, 0), sC=(dd, 0))
-        ops.bgemm(t1[0], f["Vr"], xt_next, d, d, d, lda=d, ldb=d, ldc=d, transb=True, batch=bc, sA=(dd, 0), sC=(dd, 0))
+        _right(_left(f["Vl"], hat[0], d, d, bc, out=t1[0]), f["Vr"], d, d, d, bc, out=xt_next)
 
 
 class SRConv(_SpectralPlus, A_functions):
@@ -1112,51 +1087,34 @@ class SRConv(_SpectralPlus, A_functions):
             self._t_ut, self._t_u = ut.to(dev), _inverse_perm(ut).to(dev)
         return self
 
-    def _sandwich(self, L, x, Rt, rows, cols, inner):
-        """L X R for every (b, c) plane: L [rows x inner], X [inner x inner], R given transposed as Rt [cols x inner]."""
-        bc = x.numel() // (inner * inner)
-        t1 = torch.empty(bc, rows, inner, dtype=torch.float32, device=x.device)
-        ops.bgemm(L, x, t1, rows, inner, inner, lda=inner, ldb=inner, ldc=inner, transb=False, batch=bc,
-                  sB=(inner * inner, 0), sC=(rows * inner, 0))
-        out = torch.empty(bc, rows, cols, dtype=torch.float32, device=x.device)
-        ops.bgemm(t1, Rt, out, rows, cols, inner, lda=inner, ldb=inner, ldc=cols, transb=True, batch=bc,
-                  sA=(rows * inner, 0), sC=(rows * cols, 0))
-        return out
-
     def Vt(self, vec):                                                     # :899-907: V^T X V, then P_1 and (pos, c) interleave
         sp, d = self._spectral(), self.img_dim
-        t = self._sandwich(sp._Vts, _img(vec, self.channels, d), sp._Vts, d, d, d)
+        t = _two_sided(sp._Vts, _img(vec, self.channels, d), sp._Vts, d, d, d)
         return _gather(t.reshape(vec.shape[0], -1), sp._t_vt, self._spectral_dim())
 
     def V(self, vec):                                                      # :886-897
         sp, d = self._spectral(), self.img_dim
         t = _gather(vec, sp._t_v, self._spectral_dim())
-        return self._sandwich(sp._Vs, t, sp._Vs, d, d, d).reshape(vec.shape[0], -1)
+        return _two_sided(sp._Vs, t, sp._Vs, d, d, d).reshape(vec.shape[0], -1)
 
     def Ut(self, vec):                                                     # :919-925
         sp, m = self._spectral(), self.small_dim
         y = _flat(vec)
-        t = self._sandwich(sp._Uts, y, sp._Uts, m, m, m)
+        t = _two_sided(sp._Uts, y, sp._Uts, m, m, m)
         return _gather(t.reshape(y.shape[0], -1), sp._t_ut, self.channels * m * m)
 
     def U(self, vec):                                                      # :909-917
         sp, m = self._spectral(), self.small_dim
         t = _gather(vec, sp._t_u, self.channels * m * m)
-        return self._sandwich(sp._Us, t, sp._Us, m, m, m).reshape(vec.shape[0], -1)
+        return _two_sided(sp._Us, t, sp._Us, m, m, m).reshape(vec.shape[0], -1)
 
     def add_zeros(self, vec):                                              # :930-934
         return _gather(vec, None, self._spectral_dim())
 
     def _A(self, x, y_sub=None):
-        """Y = Ae X Ae^T (- y_sub) for every (b, c) plane."""
-        B = x.shape[0]
-        bc, d, m = B * self.channels, self.img_dim, self.small_dim
-        t1 = torch.empty(bc, m, d, dtype=torch.float32, device=x.device)
-        ops.bgemm(self.Ae, x, t1, m, d, d, lda=d, ldb=d, ldc=d, transb=False, batch=bc, sB=(d * d, 0), sC=(m * d, 0))
-        y = torch.empty(B, self.channels * m * m, dtype=torch.float32, device=x.device)
-        ops.bgemm(t1, self.Ae, y, m, m, d, lda=d, ldb=d, ldc=m, transb=True, batch=bc, sA=(m * d, 0), sC=(m * m, 0),
-                  D=y_sub, ldd=m, sD=(m * m, 0), beta=-1.0)
-        return y
+        """Y = Ae X Ae^T (- y_sub, fused in the GEMM epilogue) for every (b, c) plane."""
+        d, m = self.img_dim, self.small_dim
+        return _two_sided(self.Ae, x, self.Ae, m, d, m, D=y_sub, beta=-1.0).reshape(x.shape[0], -1)
 
     def measurement_size(self):
         return self.channels * self.small_dim ** 2
@@ -1168,14 +1126,8 @@ class SRConv(_SpectralPlus, A_functions):
         return self._A(_img(vec, self.channels, self.img_dim))
 
     def A_pinv(self, vec):
-        B = vec.shape[0]
-        y = vec.reshape(B, -1).float().contiguous()
-        bc, d, m = B * self.channels, self.img_dim, self.small_dim
-        t2 = torch.empty(bc, d, m, dtype=torch.float32, device=y.device)
-        ops.bgemm(self.Pe, y, t2, d, m, m, lda=m, ldb=m, ldc=m, transb=False, batch=bc, sB=(m * m, 0), sC=(d * m, 0))
-        x = torch.empty(B, self.channels * d * d, dtype=torch.float32, device=y.device)
-        ops.bgemm(t2, self.Pe, x, d, d, m, lda=m, ldb=m, ldc=d, transb=True, batch=bc, sA=(d * m, 0), sC=(d * d, 0))
-        return x
+        d, m = self.img_dim, self.small_dim
+        return _two_sided(self.Pe, _flat(vec), self.Pe, d, m, d).reshape(vec.shape[0], -1)
 
     def _plus_factors(self):
         if not hasattr(self, "_plus_f"):
@@ -1246,17 +1198,9 @@ class Deblurring2D(_SpectralPlus, A_functions):
     def _sandwich(self, L, x, Rt_rows, gain, L2, R2_rows):
         """out = L2 . (gain .* (L . X . R)) . R2  for every plane; Rt_rows / R2_rows hold R^T / R2^T row-major
         (= the `[N][K]` operand layout of the GEMM)."""
-        bc, n = x.shape[0] * self.channels, self.img_dim
-        t1 = torch.empty(bc, n, n, dtype=torch.float32, device=x.device)
-        ops.bgemm(L, x, t1, n, n, n, lda=n, ldb=n, ldc=n, transb=False, batch=bc, sB=(n * n, 0), sC=(n * n, 0))
-        t2 = torch.empty_like(t1)
-        ops.bgemm(t1, Rt_rows, t2, n, n, n, lda=n, ldb=n, ldc=n, transb=True, batch=bc, sA=(n * n, 0), sC=(n * n, 0))
-        check(_lib.lib().ddnm_mul_planes_f32(_p(t2), _p(gain), self.channels, n * n, _p(t2), t2.numel(), ops._stream()),
-              "ddnm_mul_planes_f32")
-        ops.bgemm(L2, t2, t1, n, n, n, lda=n, ldb=n, ldc=n, transb=False, batch=bc, sB=(n * n, 0), sC=(n * n, 0))
-        out = torch.empty(x.shape[0], self.channels * n * n, dtype=torch.float32, device=x.device)
-        ops.bgemm(t1, R2_rows, out, n, n, n, lda=n, ldb=n, ldc=n, transb=True, batch=bc, sA=(n * n, 0), sC=(n * n, 0))
-        return out
+        n = self.img_dim
+        spec = _mul_planes(_two_sided(L, x, Rt_rows, n, n, n), gain, self.channels, n * n)
+        return _two_sided(L2, spec, R2_rows, n, n, n).reshape(x.shape[0], -1)
 
     def measurement_size(self):
         return self.channels * self.img_dim ** 2
@@ -1293,35 +1237,34 @@ class Deblurring(Deblurring2D):
 
     def _spectral_mix(self, x, y, a, sigma_y, sigma_t, eta, mode):
         out = torch.empty_like(x)
-        check(_lib.lib().ddnm_spectral_mix_f32(_p(x), _p(y), _p(self.S_orig), self.img_dim ** 2, _p(out), x.numel(),
-                                               float(a), float(sigma_y), float(sigma_t), float(eta), mode,
-                                               ops._stream()), "ddnm_spectral_mix_f32")
-        return out
-
-    def _two_sided(self, L, x, Rt_rows):
-        """L . X . R for every plane (Rt_rows = R^T row-major)."""
-        bc, n = x.numel() // self.img_dim ** 2, self.img_dim
-        t1 = torch.empty(bc, n, n, dtype=torch.float32, device=x.device)
-        ops.bgemm(L, x, t1, n, n, n, lda=n, ldb=n, ldc=n, transb=False, batch=bc, sB=(n * n, 0), sC=(n * n, 0))
-        out = torch.empty(x.shape[0], x.numel() // x.shape[0], dtype=torch.float32, device=x.device)
-        ops.bgemm(t1, Rt_rows, out, n, n, n, lda=n, ldb=n, ldc=n, transb=True, batch=bc, sA=(n * n, 0), sC=(n * n, 0))
+        ops.call("ddnm_spectral_mix_f32", _p(x), _p(y), _p(self.S_orig), self.img_dim ** 2, _p(out), x.numel(), float(a),
+                 float(sigma_y), float(sigma_t), float(eta), mode)
         return out
 
     def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:1016-1040
         """V diag(lambda) V^T vec, lambda from the un-thresholded singular values; the reference's sort and its
         inverse cancel, so the weights are applied directly in the (V1^T X V1) plane."""
-        spec = self._two_sided(self.V1t, _img(vec, self.channels, self.img_dim), self.V1t)
+        n = self.img_dim
+        spec = _two_sided(self.V1t, _img(vec, self.channels, n), self.V1t, n, n, n)
         spec = self._spectral_mix(spec, None, a, sigma_y, sigma_t, eta, 0)
-        return self._two_sided(self.V1, spec, self.V1)
+        return _two_sided(self.V1, spec, self.V1, n, n, n).reshape(vec.shape[0], -1)
 
     def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :1042-1091 (raw entries fed to V)
+        n = self.img_dim
         mixed = self._spectral_mix(_flat(vec), _flat(epsilon), a, sigma_y, sigma_t, eta, 1)
-        return self._two_sided(self.V1, mixed, self.V1)
+        return _two_sided(self.V1, mixed, self.V1, n, n, n).reshape(vec.shape[0], -1)
 
 
 def gaussian_taps(sigma, radius):
     """diffusion.py:507-520: fp32 exp(-0.5 (x/sigma)^2) for x = -radius..radius."""
     return torch.tensor([float(torch.exp(torch.Tensor([-0.5 * (x / sigma) ** 2]))) for x in range(-radius, radius + 1)])
+
+
+def missing_indices_of_mask(mask):
+    """2-D numpy mask (0 = missing) -> the `missing_indices` of `Inpainting`: the three HWC-interleaved entries of every
+    missing pixel (guided_diffusion/diffusion.py:465-470)."""
+    r = torch.nonzero(torch.from_numpy(mask).reshape(-1) == 0).long().reshape(-1) * 3
+    return torch.cat([r, r + 1, r + 2], dim=0)
 
 
 def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask.npy", perm=None):
@@ -1338,9 +1281,7 @@ def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask
             return InpaintingBank(c, d, mask, device)
         if mask.ndim != 2:
             raise ValueError(f"{mask_path}: a mask file is 2-D (one mask) or 3-D (a bank of masks), got {mask.ndim}-D")
-        mask = torch.from_numpy(mask).reshape(-1)
-        r = torch.nonzero(mask == 0).long().reshape(-1) * 3
-        return Inpainting(c, d, torch.cat([r, r + 1, r + 2], dim=0), device)
+        return Inpainting(c, d, missing_indices_of_mask(mask), device)
     if deg == "denoising":
         return Denoising(c, d, device)
     if deg == "colorization":

@@ -56,7 +56,7 @@ from .. import ops
 from ..functions.svd_ddnm import (_AtenNoise, _reverse_loop, _TapeNoise, ddnm_diffusion, ddnm_plus_diffusion,
                                   get_schedule_jump)
 from ..functions.svd_operators import (Colorization, Denoising, Inpainting, InpaintingBank, SuperResolution,
-                                      build_operator, mask_color_sr)
+                                      build_operator, mask_color_sr, missing_indices_of_mask)
 from .models import Model
 
 
@@ -1050,9 +1050,7 @@ class Diffusion(object):
             mask = np.load("exp/inp_masks/mask.npy")
             if mask.ndim == 3:
                 raise ValueError("per-image mask banks need the SVD path")
-            mask = torch.from_numpy(mask).reshape(-1)                                   # A = Ap = z * mask
-            r = torch.nonzero(mask == 0).long().reshape(-1) * 3
-            return Inpainting(config.data.channels, d, torch.cat([r, r + 1, r + 2], 0), dev)
+            return Inpainting(config.data.channels, d, missing_indices_of_mask(mask), dev)      # A = Ap = z * mask
         if args.deg in ("mask_color_sr", "diy"):                                         # :260-290
             mask = torch.from_numpy(np.load("exp/inp_masks/mask.npy"))
             return mask_color_sr(config.data.channels, d, mask, round(args.deg_scale), dev)

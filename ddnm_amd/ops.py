@@ -1003,6 +1003,20 @@ def step_noise_args(name, noise, like):
     return name, _p(noise)
 
 
+def call(name, *args):
+    """Checked call of the library's entry point `name` on the current stream (its last parameter)."""
+    check(getattr(_lib.lib(), name)(*args, _stream()), name)
+
+
+def step_call(name, xt, et, noise, y, *between_and_s):
+    """Checked launch of a fused sampler step `name(xt, et, et batch stride, noise, y, *between, &s, stream)`: validates
+    et's layout, picks the keyed or unkeyed entry point for `noise` (step_noise_args); the last argument is the StepScalars."""
+    *between, s = between_and_s
+    ep, es = _et_args(et)
+    fn, nz = step_noise_args(name, noise, xt)
+    check(getattr(_lib.lib(), fn)(_p(xt), ep, es, nz, _p(y), *between, ctypes.byref(s), _stream()), fn)
+
+
 def step_scalars(at, at_next, eta, lam=1.0, gamma=1.0):
     """Host-side scalar terms of one reverse step, evaluated in fp32 exactly like the reference
     (functions/svd_ddnm.py:57,63-65): `at`, `at_next` are fp32 torch scalars (alpha-bar)."""
