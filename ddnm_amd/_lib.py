@@ -5,7 +5,7 @@ or a kernel returns an error, this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libddnm_hip.so")
@@ -231,6 +231,22 @@ PROTOTYPES = {
                                                   c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
                                                   c_float, c_float, POINTER(StepScalars), c_void_p]),
     "ddnm_step_plus_cs_post_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    # demosaicing: the CFA pattern is a HOST array of ph * pw codes, copied into the kernel arguments
+    "ddnm_op_mosaic_A_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32,
+                                       c_void_p]),
+    "ddnm_op_mosaic_pinv_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32,
+                                          c_void_p]),
+    "ddnm_step_mosaic_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                       c_int32, POINTER(c_uint8), c_int32, c_int32, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_mosaic_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                             c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, POINTER(StepScalars),
+                                             c_void_p]),
+    "ddnm_step_plus_mosaic_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                            c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, c_float, c_float, c_float,
+                                            c_float, c_float, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_mosaic_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_int32, c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, c_float,
+                                                  c_float, c_float, c_float, c_float, POINTER(StepScalars), c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ddnm_op_avgpool_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_op_upsample_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

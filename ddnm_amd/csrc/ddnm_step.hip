@@ -8,6 +8,7 @@
 //   sr_averagepooling : A = r x r mean,  A^+ = replicate           (svd_operators.py:479-533)
 //   colorization      : A = w . rgb,     A^+ = w/|w|^2             (svd_operators.py:627-667)
 //   inpainting        : A = gather kept, A^+ = scatter             (svd_operators.py:324-359)
+//   demosaicing       : A = one channel per pixel (CFA), A^+ = scatter   (the same class over single entries)
 //   denoising         : identity                                    (svd_operators.py:442-462)
 // Rounding follows the reference's evaluation order; contraction into FMA is disabled so
 // that mul/add round separately like the ATen elementwise kernels.
@@ -322,6 +323,171 @@ extern "C" int ddnm_step_inpaint_pi_keyed_f32(const float* xt, const float* et, 
                                B, HW, s, stream);
 }
 
+// ---------------------------------------------------------------- fused: demosaicing (colour filter array)
+// Pixel (r, c) keeps the one channel pattern[r % ph][c % pw] (0 = R, 1 = G, 2 = B; 1 <= ph, pw <= 8): the reference's
+// Inpainting over the HWC-interleaved entries with the two unsampled entries of every pixel missing
+// (svd_operators.py:324-359), so y[b][p] = x[b][cfa(p)][p] in pixel order and every singular value is 1.  The pattern
+// travels by value in the kernel arguments, two bits per site of the period: no table is read.
+struct Cfa {
+    uint64_t w[2];   // code of site k = r % ph * pw + c % pw: bits 2 (k & 31) .. of w[k >> 5]
+    int ph, pw;
+};
+
+// DDNM_E_SHAPE for a period outside 1..8 or a code above 2 (the caller has checked the pointer)
+static int cfa_pack(const uint8_t* pattern_host, int32_t ph, int32_t pw, Cfa* out) {
+    if (ph < 1 || ph > 8 || pw < 1 || pw > 8) return DDNM_E_SHAPE;
+    Cfa c{{0, 0}, ph, pw};
+    for (int k = 0; k < ph * pw; ++k) {
+        if (pattern_host[k] > 2) return DDNM_E_SHAPE;
+        c.w[k >> 5] |= (uint64_t)pattern_host[k] << (2 * (k & 31));
+    }
+    *out = c;
+    return 0;
+}
+
+// channel codes of the four pixels p4 * 4 .. + 3 of an image (one row: W % 4 == 0)
+__device__ __forceinline__ void cfa_codes(const Cfa& f, int64_t p4, int W, int code[4]) {
+    const int64_t pix = p4 * 4;
+    const int r = (int)(pix / W);
+    int cc = (int)(pix - (int64_t)r * W) % f.pw;
+    const int row = r % f.ph * f.pw;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = row + cc;
+        code[j] = (int)(((k < 32 ? f.w[0] : f.w[1]) >> (2 * (k & 31))) & 3);
+        cc = cc + 1 == f.pw ? 0 : cc + 1;
+    }
+}
+
+// one thread per four consecutive pixels of all three planes, one float4 of y: 13 planes of HW floats per image with
+// in-kernel noise and x0 written (xt, et: 6 read; y: 1; x0, xt': 6 written)
+template <class NZ>
+__global__ __launch_bounds__(256) void step_mosaic_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                          int64_t et_bstride, NZ noise,
+                                                          const float* __restrict__ y, float* __restrict__ x0o,
+                                                          float* __restrict__ xn, int W, int64_t hw4, int64_t total4,
+                                                          ddnm_step_scalars s, Cfa cfa) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / hw4, p = i - b * hw4;
+        const auto nz = bind(noise, b);
+        const int64_t base = (b * 3 * hw4 + p) * 4, ebase = b * et_bstride + p * 4;
+        const f32x4 yv = ld4(y + i * 4);
+        int code[4];
+        cfa_codes(cfa, p, W, code);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f32x4 e = ld4(et + ebase + c * hw4 * 4);
+            const f32x4 x0 = x0_of(ld4(xt + base + c * hw4 * 4), e, s);
+            if (x0o) st4(x0o + base + c * hw4 * 4, x0);
+            f32x4 x0h = x0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (code[j] == c) x0h[j] = x0[j] - (x0[j] - yv[j]) * s.lambda;
+            st4(xn + base + c * hw4 * 4, update_of(x0h, nz4(nz, base + c * hw4 * 4), e, s));
+        }
+    }
+}
+
+// sizes and pattern of every mosaic entry point, after its pointer checks (DDNM_E_BADARG before DDNM_E_SHAPE)
+static int mosaic_args(int32_t B, int32_t H, int32_t W, int64_t et_bstride, const uint8_t* pattern_host, int32_t ph, int32_t pw,
+                       Cfa* cfa) {
+    if (!pattern_host || B <= 0 || H <= 0 || W <= 0) return DDNM_E_BADARG;
+    if ((H & 3) || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    return cfa_pack(pattern_host, ph, pw, cfa);
+}
+
+template <class Src>
+static int launch_step_mosaic(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0, float* xt_next,
+                              int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host, int32_t ph, int32_t pw,
+                              const ddnm_step_scalars* s, void* stream) {
+    Cfa cfa;
+    if (int e = mosaic_args(B, H, W, et_bstride, pattern_host, ph, pw, &cfa)) return e;
+    const int64_t hw4 = (int64_t)H * W / 4, total4 = B * hw4;
+    DDNM_LAUNCH(step_mosaic_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, x0, xt_next,
+                W, hw4, total4, *s, cfa);
+    return 0;
+}
+
+extern "C" int ddnm_step_mosaic_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                                    float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host,
+                                    int32_t ph, int32_t pw, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_mosaic(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, x0, xt_next, B, H, W, pattern_host, ph,
+                              pw, s, stream);
+}
+
+// The whole DDNM+ reverse step (functions/svd_ddnm.py:118-131) of the mosaic: every singular value is 1, so Lambda and
+// Lambda_noise are diagonal in the image (svd_operators.py:361-439) and with a = sqrt_at_next, n ~ N(0, I),
+// (lambda, d1r, d2r) on the sampled entries and (1, d1n, d2n) on the others
+//   x0      = (x_t - eps * sqrt_1m_at) / sqrt_at                       (written uncorrected)
+//   x_{t-1} = a x0 - a lambda (x0 - y) + d1r n + d2r eps               sampled entries
+//   x_{t-1} = a x0 + d1n n + d2n eps                                   the other entries
+// The five coefficients come from the host (svd_operators.cs_plus_coefficients), like CsPlusCoef.
+struct CsPlusCoef { float al, d1n, d2n, dd1, dd2; };   // a*lambda, d1n, d2n, d1r - d1n, d2r - d2n
+
+template <class NZ>
+__global__ __launch_bounds__(256) void step_plus_mosaic_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                               int64_t et_bstride, NZ noise,
+                                                               const float* __restrict__ y, float* __restrict__ x0o,
+                                                               float* __restrict__ xn, int W, int64_t hw4, int64_t total4,
+                                                               ddnm_step_scalars s, Cfa cfa, CsPlusCoef k) {
+    const float a = s.sqrt_at_next, d1r = k.d1n + k.dd1, d2r = k.d2n + k.dd2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / hw4, p = i - b * hw4;
+        const auto nz = bind(noise, b);
+        const int64_t base = (b * 3 * hw4 + p) * 4, ebase = b * et_bstride + p * 4;
+        const f32x4 yv = ld4(y + i * 4);
+        int code[4];
+        cfa_codes(cfa, p, W, code);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f32x4 e = ld4(et + ebase + c * hw4 * 4);
+            const f32x4 x0 = x0_of(ld4(xt + base + c * hw4 * 4), e, s);
+            st4(x0o + base + c * hw4 * 4, x0);
+            const f32x4 n = nz4(nz, base + c * hw4 * 4);
+            f32x4 al, d1, d2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool m = code[j] == c;
+                al[j] = m ? k.al : 0.f;
+                d1[j] = m ? d1r : k.d1n;
+                d2[j] = m ? d2r : k.d2n;
+            }
+            st4(xn + base + c * hw4 * 4, ((x0 * a - (x0 - yv) * al) + n * d1) + e * d2);
+        }
+    }
+}
+
+template <class Src>
+static int launch_step_plus_mosaic(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0_out,
+                                   float* xt_next, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host, int32_t ph,
+                                   int32_t pw, CsPlusCoef k, const ddnm_step_scalars* s, void* stream) {
+    Cfa cfa;
+    if (int e = mosaic_args(B, H, W, et_bstride, pattern_host, ph, pw, &cfa)) return e;
+    const int64_t hw4 = (int64_t)H * W / 4, total4 = B * hw4;
+    DDNM_LAUNCH(step_plus_mosaic_kernel<Src>, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, x0_out,
+                xt_next, W, hw4, total4, *s, cfa, k);
+    return 0;
+}
+
+extern "C" int ddnm_step_plus_mosaic_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                         const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                         const uint8_t* pattern_host, int32_t ph, int32_t pw, float a_lambda, float d1n,
+                                         float d2n, float dd1, float dd2, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !x0_out || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_plus_mosaic(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, x0_out, xt_next, B, H, W,
+                                   pattern_host, ph, pw, CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2}, s, stream);
+}
+
+extern "C" int ddnm_step_plus_mosaic_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                               const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                               const uint8_t* pattern_host, int32_t ph, int32_t pw, float a_lambda, float d1n,
+                                               float d2n, float dd1, float dd2, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !x0_out || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_plus_mosaic(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, x0_out, xt_next, B, H, W,
+                                   pattern_host, ph, pw, CsPlusCoef{a_lambda, d1n, d2n, dd1, dd2}, s, stream);
+}
+
 // ---------------------------------------------------------------- fused: denoising (A = I)
 template <class NZ>
 __global__ __launch_bounds__(256) void step_denoise_kernel(const float* __restrict__ xt, const float* __restrict__ et,
@@ -387,6 +553,15 @@ extern "C" int ddnm_step_inpaint_keyed_f32(const float* xt, const float* et, int
     if ((HW & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
     return launch_step_inpaint(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * HW), y, (int64_t)3 * n_kept, rank, (int64_t)0, x0,
                                xt_next, B, HW, s, stream);
+}
+
+extern "C" int ddnm_step_mosaic_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                          const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                          const uint8_t* pattern_host, int32_t ph, int32_t pw, const ddnm_step_scalars* s,
+                                          void* stream) {
+    if (!xt || !et || !y || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_mosaic(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, x0, xt_next, B, H, W, pattern_host, ph,
+                              pw, s, stream);
 }
 
 extern "C" int ddnm_step_denoise_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
@@ -628,6 +803,65 @@ extern "C" int ddnm_op_inpaint_pinv_pi_f32(const float* y, int64_t y_stride, con
     const int64_t total = (int64_t)B * HW;
     DDNM_LAUNCH(inpaint_pinv_kernel, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, y, y_stride, rank, (int64_t)HW, x,
                 (int64_t)HW, total);
+    return 0;
+}
+
+// A and A^+ of the mosaic: y[b][p] = x[b][cfa(p)][p]; A^+ writes y[p] to plane cfa(p) and 0 to the other two.  One thread
+// per four pixels, float4 on both sides.
+__global__ __launch_bounds__(256) void mosaic_A_kernel(const float* __restrict__ x, float* __restrict__ y, int W, int64_t hw4,
+                                                       int64_t total4, Cfa cfa) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / hw4, p = i - b * hw4;
+        const int64_t base = (b * 3 * hw4 + p) * 4;
+        int code[4];
+        cfa_codes(cfa, p, W, code);
+        f32x4 v = ld4(x + base);
+#pragma unroll
+        for (int c = 1; c < 3; ++c) {
+            const f32x4 xc = ld4(x + base + c * hw4 * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (code[j] == c) v[j] = xc[j];
+        }
+        st4(y + i * 4, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void mosaic_pinv_kernel(const float* __restrict__ y, float* __restrict__ x, int W, int64_t hw4,
+                                                          int64_t total4, Cfa cfa) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / hw4, p = i - b * hw4;
+        const int64_t base = (b * 3 * hw4 + p) * 4;
+        int code[4];
+        cfa_codes(cfa, p, W, code);
+        const f32x4 yv = ld4(y + i * 4);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = code[j] == c ? yv[j] : 0.f;
+            st4(x + base + c * hw4 * 4, v);
+        }
+    }
+}
+
+extern "C" int ddnm_op_mosaic_A_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host,
+                                    int32_t ph, int32_t pw, void* stream) {
+    if (!x || !y) return DDNM_E_BADARG;
+    Cfa cfa;
+    if (int e = mosaic_args(B, H, W, 0, pattern_host, ph, pw, &cfa)) return e;
+    const int64_t hw4 = (int64_t)H * W / 4, total4 = B * hw4;
+    DDNM_LAUNCH(mosaic_A_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, x, y, W, hw4, total4, cfa);
+    return 0;
+}
+
+extern "C" int ddnm_op_mosaic_pinv_f32(const float* y, float* x, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host,
+                                       int32_t ph, int32_t pw, void* stream) {
+    if (!x || !y) return DDNM_E_BADARG;
+    Cfa cfa;
+    if (int e = mosaic_args(B, H, W, 0, pattern_host, ph, pw, &cfa)) return e;
+    const int64_t hw4 = (int64_t)H * W / 4, total4 = B * hw4;
+    DDNM_LAUNCH(mosaic_pinv_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, y, x, W, hw4, total4, cfa);
     return 0;
 }
 
@@ -1030,8 +1264,8 @@ extern "C" int ddnm_patchify_f32(const float* src, float* dst, int32_t planes, i
 //   x_{t-1} = a x0 + d1n n + d2n eps + a lambda A^+ y + unpatch((w M^T) M)
 // = a (x0 - Lambda A^+ (A x0 - y)) + V (d1 .* V^T n + d2 .* V^T eps) without the full V_small.  The pre kernel writes x0,
 // the image-order part of x_{t-1} and w; two ddnm_bgemm_f32 launches (the products of CS.A / CS.A_pinv) project w; the
-// post kernel adds the projection.  The five coefficients come from the host (svd_operators.cs_plus_coefficients).
-struct CsPlusCoef { float al, d1n, d2n, dd1, dd2; };   // a*lambda, d1n, d2n, d1r - d1n, d2r - d2n
+// post kernel adds the projection.  The five coefficients come from the host (svd_operators.cs_plus_coefficients):
+// CsPlusCoef, defined above with the mosaic step that shares it.
 
 // one float4 per lane in image order [B][C][D][D]: 3 reads (+ the noise tensor), 3 writes; four consecutive pixels of a
 // row stay inside one patch row (ps % 4 == 0), so the store into w is one 16-byte piece at patchify_kernel's position

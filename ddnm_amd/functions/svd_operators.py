@@ -13,6 +13,8 @@ as one (or a few) hand-written HIP kernels:
   Inpainting       -> gather / scatter through a rank table      (svd_operators.py:324-359)
   InpaintingBank / PerImageInpainting -> the same with one mask (rank table) per image of the batch; the reference
                       holds one mask per run, so each image is checked against its single-mask operator
+  Mosaic           -> demosaicing: that Inpainting over single entries, one colour sample per pixel behind a periodic
+                      colour filter array; no table, y is a dense one-channel picture; `ddnm_plus_step` is ONE kernel
   WalshHadamardCS  -> separable FWHT (shuffle + LDS) + permuted mask (svd_operators.py:211-251)
   Denoising        -> identity                                   (svd_operators.py:442-462)
 
@@ -479,7 +481,40 @@ def _rank_table(keep):
     return rank.to(torch.int32)
 
 
-class Inpainting(A_functions):
+class _MissingEntries(A_functions):
+    """The spectral surface of the reference's Inpainting (svd_operators.py:324-359) for ANY set of missing entries of the
+    HWC-interleaved image: whole pixels (Inpainting) or the two colour entries a filter array does not sample (Mosaic).
+    A subclass sets `missing_indices`, `img_dim` and `device`."""
+
+    def _tables(self):
+        """Vt = the permutation [kept (ascending HWC-interleaved index), missing (in `missing_indices` order)] of the
+        HWC-interleaved image (svd_operators.py:339-344); V its inverse."""
+        if not hasattr(self, "_t_vt"):
+            hw = self.img_dim ** 2
+            miss = self.missing_indices.detach().cpu().long()
+            keep = torch.ones(3 * hw, dtype=torch.bool)
+            keep[miss] = False
+            order = torch.cat([torch.nonzero(keep).reshape(-1), miss])          # spectral position -> HWC index
+            img = ((order % 3) * hw + order // 3).to(torch.int32)               # HWC index p*3 + c -> CHW index c*HW + p
+            self._t_vt, self._t_v = img.to(self.device), _inverse_perm(img).to(self.device)
+        return self._t_vt, self._t_v
+
+    def Vt(self, vec):
+        return _gather(vec, self._tables()[0], self._spectral_dim())
+
+    def V(self, vec):                                                      # :332-337
+        return _gather(vec, self._tables()[1], self._spectral_dim())
+
+    def U(self, vec):                                                      # :346-350
+        return _flat(vec).clone()
+
+    Ut = U
+
+    def add_zeros(self, vec):                                              # :355-359
+        return _gather(vec, None, self._spectral_dim())
+
+
+class Inpainting(_MissingEntries):
     def __init__(self, channels, img_dim, missing_indices, device):
         if channels != 3:
             raise NotImplementedError("Inpainting kernels assume 3 channels")
@@ -521,33 +556,6 @@ class Inpainting(A_functions):
 
     def singulars(self):
         return torch.ones(3 * self.n_kept, device=self.device)
-
-    def _tables(self):
-        """Vt = the permutation [kept (ascending HWC-interleaved index), missing (in `missing_indices` order)] of the
-        HWC-interleaved image (svd_operators.py:339-344); V its inverse."""
-        if not hasattr(self, "_t_vt"):
-            hw = self.img_dim ** 2
-            miss = self.missing_indices.detach().cpu().long()
-            keep = torch.ones(3 * hw, dtype=torch.bool)
-            keep[miss] = False
-            order = torch.cat([torch.nonzero(keep).reshape(-1), miss])          # spectral position -> HWC index
-            img = ((order % 3) * hw + order // 3).to(torch.int32)               # HWC index p*3 + c -> CHW index c*HW + p
-            self._t_vt, self._t_v = img.to(self.device), _inverse_perm(img).to(self.device)
-        return self._t_vt, self._t_v
-
-    def Vt(self, vec):
-        return _gather(vec, self._tables()[0], self._spectral_dim())
-
-    def V(self, vec):                                                      # :332-337
-        return _gather(vec, self._tables()[1], self._spectral_dim())
-
-    def U(self, vec):                                                      # :346-350
-        return _flat(vec).clone()
-
-    Ut = U
-
-    def add_zeros(self, vec):                                              # :355-359
-        return _gather(vec, None, self._spectral_dim())
 
     def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:361-387
         return _mask_lambda(vec, None, self.kept_mask, 1, self.img_dim ** 2, a, sigma_y, sigma_t, eta)
@@ -688,6 +696,125 @@ class PerImageInpainting(A_functions):
             raise ValueError(f"y must be [{B}, {self.y_dim}], got {tuple(y.shape)}")
         ops.step_call("ddnm_step_inpaint_pi_f32", xt, et, noise, y, self.y_dim, _p(self.rank), max(self.n_kept), _p(x0_out),
                       _p(xt_next), B, self.img_dim ** 2, s)
+
+
+# Colour filter arrays by name: [ph, pw] channel codes (0 = R, 1 = G, 2 = B), pixel (r, c) samples pattern[r % ph][c % pw].
+# `xtrans` (20 G, 8 R and 8 B per 6 x 6 period) is this project's definition of the name.
+_G, _R, _B = 1, 0, 2
+CFA_PATTERNS = {
+    "rggb": [[0, 1], [1, 2]],
+    "bggr": [[2, 1], [1, 0]],
+    "grbg": [[1, 0], [2, 1]],
+    "gbrg": [[1, 2], [0, 1]],
+    "xtrans": [[_G, _B, _G, _G, _R, _G],
+               [_R, _G, _R, _B, _G, _B],
+               [_G, _B, _G, _G, _R, _G],
+               [_G, _R, _G, _G, _B, _G],
+               [_B, _G, _B, _R, _G, _R],
+               [_G, _R, _G, _G, _B, _G]],
+}
+CFA_MAX_PERIOD = 8
+
+
+def cfa_pattern(pattern):
+    """A name of CFA_PATTERNS or a 2-D integer array -> the validated uint8 array [ph, pw] of channel codes."""
+    if isinstance(pattern, str):
+        if pattern not in CFA_PATTERNS:
+            raise ValueError(f"unknown colour filter array {pattern!r}: the named ones are {', '.join(CFA_PATTERNS)}")
+        pattern = CFA_PATTERNS[pattern]
+    p = np.asarray(pattern)
+    if p.ndim != 2 or p.dtype.kind not in "iu" or p.size == 0:
+        raise ValueError(f"a colour filter array is a 2-D integer array of channel codes, got shape {p.shape} of {p.dtype}")
+    if max(p.shape) > CFA_MAX_PERIOD:
+        raise ValueError(f"the period of a colour filter array is 1 to {CFA_MAX_PERIOD} pixels each way, got {p.shape[0]} x "
+                         f"{p.shape[1]}")
+    if p.min() < 0 or p.max() > 2:
+        raise ValueError("the channel codes of a colour filter array are 0 (R), 1 (G) and 2 (B), got "
+                         f"{sorted(set(int(v) for v in p.reshape(-1)))}")
+    return np.ascontiguousarray(p, dtype=np.uint8)
+
+
+class Mosaic(_MissingEntries):
+    """Demosaicing: a raw sensor frame keeps ONE colour sample per pixel, behind the periodic colour filter array
+    `pattern` (a name of CFA_PATTERNS or a [ph, pw] array of channel codes).  It is the reference's Inpainting
+    (svd_operators.py:324-439) over the HWC-interleaved entries with the two channels a pixel does not sample missing:
+    `missing_indices` holds those entries 3p + c in ascending order, y[b][p] = x[b][cfa(p)][p] in pixel order, A^+ the
+    scatter back, every singular value 1.  The sampling set is periodic, so the kernels derive it from the pattern in
+    their arguments (no rank table) and read y as a dense one-channel picture; the whole DDNM+ step is diagonal in the
+    image and runs as ONE kernel (`ddnm_plus_step`).  A pattern that never samples a channel leaves it in the null space."""
+
+    def __init__(self, channels, img_dim, pattern, device):
+        if channels != 3:
+            raise ValueError(f"a colour filter array samples RGB images: channels must be 3, got {channels}")
+        if img_dim % 4:
+            raise ValueError(f"Mosaic kernels handle four pixels of a row at once: img_dim must be a multiple of 4, got {img_dim}")
+        self.channels, self.img_dim, self.device = channels, img_dim, device
+        self.pattern = cfa_pattern(pattern)
+        ph, pw = self.pattern.shape
+        self._cfa = ((ctypes.c_uint8 * (ph * pw))(*[int(v) for v in self.pattern.reshape(-1)]), ph, pw)
+        r, c = np.divmod(np.arange(img_dim ** 2), img_dim)
+        code = torch.from_numpy(self.pattern[r % ph, c % pw].astype(np.int64))              # [HW]: the channel pixel p samples
+        sampled = torch.arange(3)[:, None] == code[None, :]                                   # [3][HW]
+        self.sampled_mask = sampled.float().to(device).contiguous()
+        self.missing_indices = torch.nonzero(~sampled.t().reshape(-1)).reshape(-1)            # HWC entries 3p + c, ascending
+
+    def measurement_size(self):
+        return self.img_dim ** 2
+
+    def measurement_image_shape(self):
+        return (1, self.img_dim, self.img_dim)
+
+    def A(self, vec):
+        x = _img(vec, 3, self.img_dim)
+        B, d = x.shape[0], self.img_dim
+        y = torch.empty(B, d * d, dtype=torch.float32, device=x.device)
+        ops.call("ddnm_op_mosaic_A_f32", _p(x), _p(y), B, d, d, *self._cfa)
+        return y
+
+    def A_pinv(self, vec):
+        y = _flat(vec)
+        B, d = y.shape[0], self.img_dim
+        if y.shape[1] != d * d:
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, a {d} x {d} mosaic has {d * d}")
+        x = torch.empty(B, 3 * d * d, dtype=torch.float32, device=y.device)
+        ops.call("ddnm_op_mosaic_pinv_f32", _p(y), _p(x), B, d, d, *self._cfa)
+        return x
+
+    def singulars(self):
+        return torch.ones(self.img_dim ** 2, device=self.device)
+
+    def Lambda(self, vec, a, sigma_y, sigma_t, eta):                       # svd_operators.py:361-387
+        return _mask_lambda(vec, None, self.sampled_mask, 3, self.img_dim ** 2, a, sigma_y, sigma_t, eta)
+
+    def Lambda_noise(self, vec, a, sigma_y, sigma_t, eta, epsilon):        # :389-439
+        return _mask_lambda(vec, epsilon, self.sampled_mask, 3, self.img_dim ** 2, a, sigma_y, sigma_t, eta)
+
+    def _check_y(self, y, B):
+        if y.shape[0] != B or y.numel() != B * self.img_dim ** 2:
+            raise ValueError(f"y must be [{B}, {self.img_dim ** 2}], got {tuple(y.shape)}")
+        return ops._f32c(y, "y")
+
+    def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
+        B, d = xt.shape[0], self.img_dim
+        ops.step_call("ddnm_step_mosaic_f32", xt, et, noise, self._check_y(y, B), _p(x0_out), _p(xt_next), B, d, d, *self._cfa, s)
+
+    # ---- DDNM+ (sigma_y > 0): the engine hook of `ddnm_plus_diffusion`.  Lambda / Lambda_noise above stay callable (the
+    # reference's object protocol); the loop takes the one fused launch instead of their eight.
+    def begin_plus_run(self, y):
+        y = _flat(y)
+        self._plus_run = (y.shape[0], self._check_y(y, y.shape[0]))
+
+    def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
+        """One DDNM+ reverse step in one launch: x0|t into `x0_out` (uncorrected, as the loop returns and time-travels
+        from it), x_{t-1} into `xt_next`; `et` may be the [:, :3] view of a 6-channel network output."""
+        B, d = xt.shape[0], self.img_dim
+        y, = _plus_state(self, B)
+        for name, t in (("xt", xt), ("x0_out", x0_out), ("xt_next", xt_next)):
+            if ops._f32c(t, name).numel() != 3 * B * d * d:
+                raise ValueError(f"ddnm_plus_step: {name} has {t.numel()} entries, expected {3 * B * d * d}")
+        coef = cs_plus_coefficients(s.sqrt_at_next, sigma_y, sigma_t, eta)
+        ops.step_call("ddnm_step_plus_mosaic_f32", xt, et, noise, y, _p(x0_out), _p(xt_next), B, d, d, *self._cfa,
+                      *(float(v) for v in coef), s)
 
 
 class WalshHadamardCS(A_functions):
@@ -1267,9 +1394,35 @@ def missing_indices_of_mask(mask):
     return torch.cat([r, r + 1, r + 2], dim=0)
 
 
-def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask.npy", perm=None):
-    """Operator factory of guided_diffusion/diffusion.py:451-523 for the --deg values on the hot path."""
+DEMOSAIC = "demosaic"
+
+
+def demosaic_choices():
+    return [DEMOSAIC] + [f"{DEMOSAIC}_{name}" for name in CFA_PATTERNS]
+
+
+def demosaic_pattern(deg, cfa_path="exp/cfa/pattern.npy"):
+    """The colour filter array of `--deg demosaic_<name>` (a name of CFA_PATTERNS) or of `--deg demosaic` (the 2-D integer
+    array in `cfa_path`); a ValueError that names the valid choices otherwise."""
+    valid = f"the demosaicing tasks are {', '.join(demosaic_choices())} ({DEMOSAIC} alone reads {cfa_path})"
+    if deg == DEMOSAIC:
+        try:
+            return cfa_pattern(np.load(cfa_path, allow_pickle=False))
+        except (OSError, ValueError) as e:
+            raise ValueError(f"--deg {deg}: {cfa_path} does not hold a colour filter array ({e}); {valid}") from e
+    name = deg[len(DEMOSAIC) + 1:]
+    if not deg.startswith(DEMOSAIC + "_") or name not in CFA_PATTERNS:
+        raise ValueError(f"--deg {deg}: unknown colour filter array; {valid}")
+    return cfa_pattern(name)
+
+
+def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask.npy", perm=None,
+                   cfa_path="exp/cfa/pattern.npy"):
+    """Operator factory of guided_diffusion/diffusion.py:451-523 for the --deg values on the hot path, and of the
+    demosaicing tasks (`demosaic_<cfa name>`, `demosaic`: deg_scale is ignored)."""
     c, d = config.data.channels, config.data.image_size
+    if deg.startswith(DEMOSAIC):
+        return Mosaic(c, d, demosaic_pattern(deg, cfa_path), device)
     if deg == "cs_walshhadamard":
         compress_by = round(1 / deg_scale)
         if perm is None:

@@ -35,7 +35,11 @@ Deliberate differences at the boundary (not in the results):
   * DDNM_METRICS=cons reports the data consistency of every restoration, the one figure of merit that needs no ground
     truth (and the one a run over given measurements reports unasked): `Cons: %.3e`, the running mean of
     sum |A x^ - y| / (2 n) over the n valid entries of an image's measurement ([0, 1] scale), `Total Average Cons` and
-    `Max Cons`, the largest max |A x^ - y| / 2 of the run (ops.consistency, csrc/metrics.hip).
+    `Max Cons`, the largest max |A x^ - y| / 2 of the run (ops.consistency, csrc/metrics.hip);
+  * `--deg demosaic_rggb | demosaic_bggr | demosaic_grbg | demosaic_gbrg | demosaic_xtrans` (and `--deg demosaic` with
+    the pattern of `exp/cfa/pattern.npy`) restores a raw sensor frame, one colour sample per pixel (svd_operators.Mosaic):
+    the reference's Inpainting over single entries, so every switch above applies; its measurement is a one-channel
+    S x S picture, and `Apy_{i}.png` shows the coloured mosaic.
 
 All of these run through ONE path of `Diffusion.svd_based_ddnm_plus`: the plan (`fuse_groups`: which loader batches this
 rank restores, grouped into sampler calls; `restored_images` is the same plan as image indices), `prepare` (a loader batch
@@ -55,7 +59,7 @@ from .. import dist as ddist
 from .. import ops
 from ..functions.svd_ddnm import (_AtenNoise, _reverse_loop, _TapeNoise, ddnm_diffusion, ddnm_plus_diffusion,
                                   get_schedule_jump)
-from ..functions.svd_operators import (Colorization, Denoising, Inpainting, InpaintingBank, SuperResolution,
+from ..functions.svd_operators import (DEMOSAIC, Colorization, Denoising, Inpainting, InpaintingBank, SuperResolution,
                                       build_operator, mask_color_sr, missing_indices_of_mask)
 from .models import Model
 
@@ -310,7 +314,11 @@ class MeasurementFolder(data.Dataset):
             else:
                 from PIL import Image
                 with Image.open(path) as img:
-                    w, h = img.size
+                    (w, h), bands = img.size, img.getbands()
+                if shape[0] == 1 and len(bands) != 1:
+                    # (a luminance conversion is no operator's measurement: a grey frame is taken as it is, nothing else)
+                    raise ValueError(f"{path} holds {len(bands)} channels ({''.join(bands)}), the operator's measurement "
+                                     f"has 1: nothing is converted")
                 if (h, w) != tuple(shape[1:]):
                     raise ValueError(f"{path} is {w} x {h} pixels (width x height), the operator's measurement is "
                                      f"{shape[2]} x {shape[1]}: nothing is resized or cropped")
@@ -849,7 +857,8 @@ class Diffusion(object):
             Apy = y.view(b, C, S, S)
         elif args.deg == "colorization":
             Apy = y.view(b, 1, S, S).repeat(1, 3, 1, 1)
-        elif args.deg == "inpainting":
+        elif args.deg == "inpainting" or args.deg.startswith(DEMOSAIC):
+            # entries that are not measured are shown black (a mosaic: each pixel in the colour it samples)
             Apy = Apy + A_funcs.A_pinv(A_funcs.A(torch.ones_like(Apy))).reshape(*Apy.shape) - 1
         for i in range(b):
             save_image(ops.finalize_psnr(Apy[i:i + 1].contiguous())[0][0],
@@ -1051,6 +1060,8 @@ class Diffusion(object):
             if mask.ndim == 3:
                 raise ValueError("per-image mask banks need the SVD path")
             return Inpainting(config.data.channels, d, missing_indices_of_mask(mask), dev)      # A = Ap = z * mask
+        if args.deg.startswith(DEMOSAIC):                                                # A / Ap of the Mosaic operator
+            return build_operator(args.deg, args.deg_scale, config, dev)
         if args.deg in ("mask_color_sr", "diy"):                                         # :260-290
             mask = torch.from_numpy(np.load("exp/inp_masks/mask.npy"))
             return mask_color_sr(config.data.channels, d, mask, round(args.deg_scale), dev)

@@ -30,7 +30,8 @@ extern "C" {
 
 int ddnm_version(void);                 /* ABI version, currently 7 (bumped on every struct / prototype change; the
                                            per-image inpainting entry points *_pi_* were added under 7: new symbols
-                                           only, no struct and no existing prototype changed) */
+                                           only, no struct and no existing prototype changed; the demosaicing entry
+                                           points *_mosaic_* likewise) */
 const char* ddnm_build_digest(void);    /* sha256 of the sources + flags this binary was built from (build.py) */
 int ddnm_sizeof(int which);             /* sizeof of 0: ddnm_conv_desc, 1: ddnm_gemm_desc, 2: ddnm_conv16_desc,
                                            3: ddnm_step_scalars as compiled into the binary (-1: unknown index) */
@@ -668,6 +669,55 @@ int ddnm_step_plus_cs_pre_keyed_f32(const float* xt, const float* et, int64_t et
                                     int32_t D, int32_t ps, float a_lambda, float d1n, float d2n, float dd1, float dd2,
                                     const ddnm_step_scalars* s, void* stream);
 int ddnm_step_plus_cs_post_f32(const float* P, float* xt_next, int32_t planes, int32_t D, int32_t ps, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Demosaicing: one colour sample per pixel behind a colour filter array (CFA).  The operator is the reference's
+ * Inpainting(channels, img_dim, missing_indices, device) (functions/svd_operators.py:324-439) with the indices 3p + c
+ * of the two channels c that pixel p does NOT sample: y[b][p] = x[b][cfa(p)][p] in pixel order, A^+ the scatter back,
+ * every singular value 1.  Added under ABI 7 like the *_pi_* entry points: new symbols only.
+ *   pattern_host: HOST pointer to ph * pw channel codes, row-major (0 = R, 1 = G, 2 = B), 1 <= ph, pw <= 8; pixel (r, c)
+ *                 samples channel pattern_host[(r % ph) * pw + c % pw].  It is copied by value into the kernel
+ *                 arguments (like w3_host); no device table exists.
+ *   x [B][3][H][W], y [B][H*W], et row b at et + b*et_bstride (the [:, :3] view of a 6-channel output).
+ * NULL pointer (pattern_host included), B, H or W <= 0, no noise source: DDNM_E_BADARG; then H % 4, W % 4 or
+ * et_bstride % 4 != 0, ph or pw outside 1..8, a code above 2: DDNM_E_SHAPE.  All of it is checked before any launch.
+ * ------------------------------------------------------------------------- */
+/* A and A^+ (functions/svd_operators.py:324-439: A :52-58 with V^T / U of :339-350; the DDNM+ loop of
+ * functions/svd_ddnm.py:80-164 applies them through ddnm_step_plus_mosaic_f32 instead). */
+int ddnm_op_mosaic_A_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host,
+                         int32_t ph, int32_t pw, void* stream);
+int ddnm_op_mosaic_pinv_f32(const float* y, float* x, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host,
+                            int32_t ph, int32_t pw, void* stream);
+/* Fused noise-free step (functions/svd_ddnm.py:57-65 with the operator of functions/svd_operators.py:324-439; the
+ * sigma_y > 0 loop of functions/svd_ddnm.py:80-164 takes ddnm_step_plus_mosaic_f32): one thread per four consecutive
+ * pixels of all three planes and one float4 of y,
+ *   x0 = (xt - et * sqrt_1m_at) / sqrt_at;   x0h = x0 - (x0 - y) * lambda on the plane a pixel samples, x0 elsewhere;
+ *   xt' = sqrt_at_next * x0h + c1 * noise + c2 * et.
+ * x0 (optional) receives the uncorrected x0; noise as in ddnm_step_inpaint_f32 / _keyed_f32. */
+int ddnm_step_mosaic_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                         float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host,
+                         int32_t ph, int32_t pw, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_mosaic_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                               const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W,
+                               const uint8_t* pattern_host, int32_t ph, int32_t pw, const ddnm_step_scalars* s,
+                               void* stream);
+/* The whole DDNM+ step (functions/svd_ddnm.py:80-164, step :118-131) with Lambda / Lambda_noise of
+ * functions/svd_operators.py:324-439 (:361-439), in ONE launch: the operator is diagonal in the image.  With
+ * a = s->sqrt_at_next, n ~ N(0, I), (lambda, d1r, d2r) the spectral coefficients of singular value 1 and (1, d1n, d2n) those
+ * of the null space,
+ *   x0      = (xt - et * sqrt_1m_at) / sqrt_at                        -> x0_out, uncorrected (required)
+ *   x_{t-1} = a x0 - a lambda (x0 - y) + d1r n + d2r et               on the plane a pixel samples
+ *   x_{t-1} = a x0 + d1n n + d2n et                                   on the other two
+ * a_lambda = a*lambda, dd1 = d1r - d1n, dd2 = d2r - d2n come from the host, as for ddnm_step_plus_cs_pre_f32; the noise
+ * sources are those of that entry point (tensor [B][3*H*W], in-kernel draw, or the keyed table). */
+int ddnm_step_plus_mosaic_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                              float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                              const uint8_t* pattern_host, int32_t ph, int32_t pw, float a_lambda, float d1n, float d2n,
+                              float dd1, float dd2, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_plus_mosaic_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                    const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                    const uint8_t* pattern_host, int32_t ph, int32_t pw, float a_lambda, float d1n,
+                                    float d2n, float dd1, float dd2, const ddnm_step_scalars* s, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * hq_demo sampler: DDPM posterior step with the DDNM core and the mask-shift tiles
