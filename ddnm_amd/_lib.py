@@ -124,6 +124,7 @@ PROTOTYPES = {
     "ddnm_conv_gather_s16_workspace_floats": (c_int64, [POINTER(ConvDesc)]),
     "ddnm_conv_gather_s16_stats_tiles": (c_int32, [POINTER(ConvDesc)]),
     "ddnm_conv_gather_s16_gemm1x1": (c_int32, [POINTER(ConvDesc)]),
+    "ddnm_conv_gather_s16_wslice": (c_int32, [POINTER(ConvDesc)]),
     "ddnm_conv16": (c_int32, [POINTER(Conv16Desc), c_void_p]),
     "ddnm_conv16_supported": (c_int32, [POINTER(Conv16Desc)]),
     "ddnm_conv16_fuses_fin": (c_int32, [POINTER(Conv16Desc)]),

@@ -38,26 +38,6 @@ constexpr int G1_MAX_CIN = 1024;                      // one workgroup owns all 
 constexpr int G1_ROUTE_MAX_CIN = 512;                 // ... and is routed up to here (measured, conv1x1_s16_routes)
 static_assert(G1_WAIT < 64, "vmcnt counts to 63");
 
-// Sum and sum of squares of the four pixels p0..p3 of one statistics tile, in the order conv_splitk_reduce_stats_kernel takes
-// them: its 256 threads are `rows` pixel rows of Cout / 4 channel columns; row r adds the pixels r, r + rows, ... (squares by
-// fma), then the rows are added in order.  No contraction here: where that kernel rounds a square by itself, so does this.
-__device__ __forceinline__ void g1_tile_stats(float p0, float p1, float p2, float p3, int rows, float& s, float& q) {
-#pragma clang fp contract(off)
-    if (rows >= 4) {
-        s = ((p0 + p1) + p2) + p3;
-        q = ((p0 * p0 + p1 * p1) + p2 * p2) + p3 * p3;
-    } else if (rows == 3) {
-        s = ((p0 + p3) + p1) + p2;
-        q = (__builtin_fmaf(p3, p3, p0 * p0) + p1 * p1) + p2 * p2;
-    } else if (rows == 2) {
-        s = (p0 + p2) + (p1 + p3);
-        q = __builtin_fmaf(p2, p2, p0 * p0) + __builtin_fmaf(p3, p3, p1 * p1);
-    } else {
-        s = ((p0 + p1) + p2) + p3;
-        q = __builtin_fmaf(p3, p3, __builtin_fmaf(p2, p2, __builtin_fmaf(p1, p1, p0 * p0)));
-    }
-}
-
 // stats_px: 0 = no statistics; 4 = one partial row per 4 consecutive pixels (the layout of the split-K reduction pass,
 // conv_common.h::splitk_stats_tiles, which the Python layer sized stats_out for); G1_BM = one per M tile (conv_epilogue's)
 __global__ __launch_bounds__(256) void conv1x1_s16_kernel(const ConvArgs p, const int stats_px) {
@@ -273,7 +253,7 @@ __global__ __launch_bounds__(256) void conv1x1_s16_kernel(const ConvArgs p, cons
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             float cs, cq;
-            g1_tile_stats(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3], rows, cs, cq);
+            s16_quad_stats(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3], rows, cs, cq);
             float2* const st = reinterpret_cast<float2*>(d.stats_out + ((size_t)(t0 + 2 * q) * d.Cout + n) * 2);
             *st = make_float2(cs, cq);
         }
@@ -312,10 +292,7 @@ __global__ __launch_bounds__(256) void conv1x1_s16_kernel(const ConvArgs p, cons
 //     DDNM_CONV_GEMM1X1 in ddnm_conv_desc::flags overrides this rule alone (the table was measured so).
 int conv1x1_s16_stats_px(const ddnm_conv_desc* d, int plan_ksplit, int plan_bm) {
     if (!d->stats_out) return 0;
-    if (plan_ksplit > 1) {
-        const int tpi = splitk_stats_tiles(d);
-        return tpi > 0 && d->Ho * d->Wo == 4 * tpi ? 4 : -1;
-    }
+    if (plan_ksplit > 1) return splitk_stats_are_quads(d) ? 4 : -1;
     return plan_bm == G1_BM ? G1_BM : -1;
 }
 

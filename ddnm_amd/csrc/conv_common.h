@@ -42,6 +42,10 @@ int conv3x3_s16_ups_subpixel_run(const ddnm_conv_desc* d, hipStream_t s);
 // `plan_ksplit`, `plan_bm`: split and M tile of the gather plan (they fix the statistics layout the caller sized)
 bool conv1x1_s16_routes(const ddnm_conv_desc* d, int plan_ksplit, int plan_bm);
 int conv1x1_s16_launch(const ddnm_conv_desc* d, int plan_ksplit, int plan_bm, int run_ksplit, hipStream_t s);
+// slices-on-waves form of the 3x3 / stride-1 launches of the 8 x 8 level (conv_s16_wslice.hip), dispatched from
+// conv_gather_s16.hip where the launch runs the plan's split (no slabs, no reduction launch)
+bool conv3x3_s16_wslice_routes(const ddnm_conv_desc* d, int plan_ksplit, int plan_bm);
+int conv3x3_s16_wslice_launch(const ddnm_conv_desc* d, int ksplit, hipStream_t s);
 // workgroups of a persistent launch: the CU count of the current device rounded down to a multiple of 8, queried once per device
 int conv_persist_grid_cus();
 
@@ -372,6 +376,13 @@ static inline int splitk_stats_tiles(const ddnm_conv_desc* d) {
     int tpi = hw / 4 < 128 ? hw / 4 : 128;
     while (tpi > 1 && hw % tpi) --tpi;
     return tpi;
+}
+
+// whether the statistics tiles of the reduction pass are 4 consecutive pixels: the layout that the kernels which replace a
+// split launch and its reduction (conv1x1_s16.hip, conv_s16_wslice.hip) fill from their own registers
+static inline bool splitk_stats_are_quads(const ddnm_conv_desc* d) {
+    const int tpi = splitk_stats_tiles(d);
+    return tpi > 0 && d->Ho * d->Wo == 4 * tpi;
 }
 
 static inline int launch_splitk_reduce(const ConvArgs& p, hipStream_t s) {

@@ -3,7 +3,8 @@
 // The layers of the celeba `Model` that the 3x3 halo kernel (conv_igemm_f16.hip, SPLIT form) does not take:
 //   * Downsample: 3x3 stride 2 with the reference's asymmetric (0,1,0,1) padding (guided_diffusion/models.py:61-71),
 //   * 1x1 convolutions: the attention blocks' q / k / v and proj_out, un-fused nin_shortcut (models.py:109,143-162),
-//   * 3x3 / stride 1 on the 8 x 8 level, where a 256-pixel tile would span several images.
+//   * 3x3 / stride 1 on the 8 x 8 level, where a 256-pixel tile would span several images -- at batch sizes whose plan is not
+//     2 ... 8 slices; with those (B = 8: 8 slices) conv_s16_wslice.hip takes them (routed in ddnm_conv_gather_s16_f32 below).
 // Arithmetic and operand formats are those of ddnm_conv3x3_s16_f32 (include/ddnm_hip.h): fp32 tensors, every operand
 // value carried as hi + lo fp16 halves, product = hi*hi' + hi*lo' + lo*hi' with fp32 accumulation, weights in the
 // split packing ([hi 32 | lo 32] halfs per (row, tap, 32-channel chunk), pre-scaled by a power of two).
@@ -228,6 +229,12 @@ extern "C" int ddnm_conv_gather_s16_gemm1x1(const ddnm_conv_desc* d) {
     return !(d->flags & DDNM_CONV_ONE_TILE) && conv1x1_s16_routes(d, pl.ksplit, pl.BM) ? 1 : 0;
 }
 
+extern "C" int ddnm_conv_gather_s16_wslice(const ddnm_conv_desc* d) {
+    PlanGS pl;
+    if (!d || !plan_gs(d, &pl)) return DDNM_E_SHAPE;
+    return !(d->flags & DDNM_CONV_ONE_TILE) && conv3x3_s16_wslice_routes(d, pl.ksplit, pl.BM) ? 1 : 0;
+}
+
 extern "C" int ddnm_conv_gather_s16_f32(const ddnm_conv_desc* d, void* stream) {
     if (int e = conv_check_desc(d)) return e;
     if (!(d->acc_scale > 0.f)) return DDNM_E_BADARG;
@@ -241,6 +248,10 @@ extern "C" int ddnm_conv_gather_s16_f32(const ddnm_conv_desc* d, void* stream) {
     // conv1x1_s16_routes says so; DDNM_CONV_ONE_TILE keeps the gather kernel below (A/B timing, comparison partner)
     if (!(d->flags & DDNM_CONV_ONE_TILE) && conv1x1_s16_routes(d, plan_ksplit, pl.BM))
         return conv1x1_s16_launch(d, plan_ksplit, pl.BM, pl.ksplit, (hipStream_t)stream);
+    // 3x3 launches of the 8 x 8 level with the plan's slices on the waves of one workgroup (conv_s16_wslice.hip), when the
+    // launch runs the plan's split (the slabs it was given room for are not written)
+    if (!(d->flags & DDNM_CONV_ONE_TILE) && pl.ksplit == plan_ksplit && conv3x3_s16_wslice_routes(d, plan_ksplit, pl.BM))
+        return conv3x3_s16_wslice_launch(d, plan_ksplit, (hipStream_t)stream);
     // tiles_x = 0: flat strips of BM consecutive pixels of one image
     const ConvArgs p = conv_args(*d, pl.BM, d->Cout / pl.BN, 32, 5, 0, d->ksize * d->ksize, pl.ksplit);
     const dim3 grid(p.m_tiles * p.n_tiles, pl.ksplit);

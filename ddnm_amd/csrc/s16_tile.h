@@ -1,5 +1,5 @@
 // The tile pieces of the split-fp16 convolution kernels, once (gfx950): conv_igemm_f16.hip <.., SPLIT> (one tile per
-// workgroup), conv_s16_persist.hip, conv_s16_subpixel.hip and conv_gather_s16.hip.  The bit identity of those kernels
+// workgroup), conv_s16_persist.hip, conv_s16_subpixel.hip, conv_gather_s16.hip, conv1x1_s16.hip and conv_s16_wslice.hip.  The bit identity of those kernels
 // (tests/test_gpu_s16*.py) is the identity of these functions; what stays in a kernel is its main loop: the request
 // stream and its tables, every wait / barrier / scheduling fence, the deferred stores.
 // Plain force-inlined functions over the kernel's own arrays and registers (taken by reference): no state of their own.
@@ -150,4 +150,24 @@ __device__ __forceinline__ void s16_store_stats(const float* stat_lds, int tid, 
 #pragma unroll
     for (int w = 0; w < S16_WM; ++w) a += stat_lds[(w * S16_BN + c) * 2 + which];
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a), r_stats, st_lane, st_soff, 0);
+}
+
+// Sum and sum of squares of the four pixels p0..p3 of one statistics tile, in the order conv_splitk_reduce_stats_kernel takes
+// them: its 256 threads are `rows` pixel rows of Cout / 4 channel columns; row r adds the pixels r, r + rows, ... (squares by
+// fma), then the rows are added in order.  No contraction here: where that kernel rounds a square by itself, so does this.
+__device__ __forceinline__ void s16_quad_stats(float p0, float p1, float p2, float p3, int rows, float& s, float& q) {
+#pragma clang fp contract(off)
+    if (rows >= 4) {
+        s = ((p0 + p1) + p2) + p3;
+        q = ((p0 * p0 + p1 * p1) + p2 * p2) + p3 * p3;
+    } else if (rows == 3) {
+        s = ((p0 + p3) + p1) + p2;
+        q = (__builtin_fmaf(p3, p3, p0 * p0) + p1 * p1) + p2 * p2;
+    } else if (rows == 2) {
+        s = (p0 + p2) + (p1 + p3);
+        q = __builtin_fmaf(p2, p2, p0 * p0) + __builtin_fmaf(p3, p3, p1 * p1);
+    } else {
+        s = ((p0 + p1) + p2) + p3;
+        q = __builtin_fmaf(p3, p3, __builtin_fmaf(p2, p2, __builtin_fmaf(p1, p1, p0 * p0)));
+    }
 }

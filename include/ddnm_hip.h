@@ -97,7 +97,9 @@ typedef struct ddnm_conv_desc {
                                packing of the upsample convolution (see ddnm_conv3x3_s16_ups_subpixel_supported)
                                ddnm_conv_gather_s16_f32: bit 0 keeps a 1x1 launch on the gather kernel, bit 2 (DDNM_CONV_GEMM1X1)
                                sends it to the GEMM form wherever that kernel has a form for it, also where the measured
-                               routing rule would not (see ddnm_conv_gather_s16_gemm1x1); bit 0 wins; for A/B timing */
+                               routing rule would not (see ddnm_conv_gather_s16_gemm1x1); bit 0 wins; for A/B timing
+                               ddnm_conv_gather_s16_f32: bit 0 also keeps a 3x3 launch of the 8 x 8 level on the gather kernel
+                               (see ddnm_conv_gather_s16_wslice) */
     /* ABI 5 -- operand-range guard of the split forms (ddnm_conv3x3_s16_f32, ddnm_conv_gather_s16_f32; ignored by every
      * other entry point).  fp16 carries |v| < 65504 only, fp32 -- the arithmetic the reference runs -- does not care, so
      * operands the kernel reads RAW (no GroupNorm in front: src0 / src1 when gn_scale is NULL, skip0 / skip1 always) are
@@ -178,7 +180,8 @@ float ddnm_conv3x3_s16_act_scale(void);   /* compile-time activation pre-scale: 
 
 /* The same arithmetic for the layers the 3x3 halo kernel does not take, as a per-tap gather (csrc/conv_gather_s16.hip):
  * Downsample's 3x3 stride 2 with (0,1,0,1) padding (guided_diffusion/models.py:61-71), the 1x1 convolutions of the
- * attention blocks and un-fused nin_shortcut (models.py:109,143-162), and 3x3 / stride 1 on the 8 x 8 level.  Same
+ * attention blocks and un-fused nin_shortcut (models.py:109,143-162), and 3x3 / stride 1 on the 8 x 8 level (in the
+ * slices-on-waves form below where the plan has 2 ... 8 slices).  Same
  * descriptor, weight packing and acc_scale as ddnm_conv3x3_s16_f32 (ksize 1 or 3, stride 1 or 2, pad as given; GroupNorm
  * prologue, concat, bias / badd / residual, statistics, split-K); no fused shortcut.
  * Needs C0 % 32 == 0, C1 % 32 == 0, Cout % 64 == 0, Ho*Wo % 64 == 0 (else: ddnm_conv2d_f32). */
@@ -195,6 +198,14 @@ int ddnm_conv_gather_s16_stats_tiles(const ddnm_conv_desc* d);
  * will), 0 when it runs the gather kernel -- always with flags & DDNM_CONV_ONE_TILE --, negative when the family refuses the
  * shape. */
 int ddnm_conv_gather_s16_gemm1x1(const ddnm_conv_desc* d);
+/* Slices-on-waves form of the 3x3 / stride 1 / pad 1 launches on 8 x 8 images whose plan splits K 2 ... 8 ways (csrc/conv_s16_wslice.hip;
+ * addition within ABI 7): one workgroup of 8 waves per (image, 32 output channels), wave w computes the plan's K slice w, the
+ * slices are added in LDS in slice order and the epilogue of the reduction pass runs in the same kernel -- no slabs, no
+ * reduction launch; same operands, workspace and statistics answers, same results bit for bit.
+ * 1 when ddnm_conv_gather_s16_f32 runs this descriptor in that form (given the workspace the plan asks for; `stats_out` and
+ * `flags` count), 0 when it runs the gather kernel -- always with flags & DDNM_CONV_ONE_TILE --, negative when the family
+ * refuses the shape. */
+int ddnm_conv_gather_s16_wslice(const ddnm_conv_desc* d);
 
 /* 1x1 convolution with fp16 MFMA operands, fp32 accumulate / output: the attention blocks' qkv and proj_out
  * Conv1d(k=1) and un-fused 1x1 shortcuts of the `use_fp16` torso (guided_diffusion/unet.py:222,283-289,301-308).
