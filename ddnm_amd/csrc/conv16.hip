@@ -1219,6 +1219,9 @@ static bool plan16(const ddnm_conv16_desc* d, Plan16* pl) {
         if (ks < 1) ks = 1;
     }
     pl->ksplit = ks;
+    // the unsplit GEMM form's epilogue reads the residual at the output pixel's own index (only the 3x3 epilogues and the
+    // split-K reductions map it through the nearest x2): refuse the launch instead of reading past a quarter-size tensor
+    if (pl->taps == 1 && ks == 1 && d->res && d->res_ups) return false;
     // Cout = 128 on 256-pixel tiles, enough of them for two workgroups per CU to matter, no fused shortcut
     // (for Cout >= 256 the same kernel with Cout / 128 channel tiles measured SLOWER than the 256-channel tile: every pixel
     // tile's halo is fetched and activated once per channel tile; tools/experiments/HISTORY.md)

@@ -251,7 +251,7 @@ typedef struct ddnm_conv16_desc {
     int32_t B, H, W;          /* OUTPUT size (= input size; the operand is H/2 x W/2 when ups) */
     int32_t Cin, Cout;
     int32_t ksize;            /* 1 or 3 */
-    int32_t ups, res_ups;
+    int32_t ups, res_ups;     /* res_ups: 3x3 launches and split-K 1x1 launches; an UNSPLIT 1x1 launch with it is refused */
     int32_t SC0, SC1;
     const void* src1;         /* fp16 NHWC [B][Hs][Ws][Cin-C0] second tensor of the concat or NULL (torch.cat, unet.py:661) */
     const float* gn_scale;    /* [B][Cin] fp32 or NULL: fused GroupNorm(+FiLM) affine of the operand (3x3 only) */
