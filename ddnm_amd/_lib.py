@@ -248,6 +248,22 @@ PROTOTYPES = {
     "ddnm_step_plus_mosaic_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_int32, c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, c_float,
                                                   c_float, c_float, c_float, c_float, POINTER(StepScalars), c_void_p]),
+    # old photo (mask, grey, pool): the mask is a device plane (NULL = all kept), the three grey weights a HOST array
+    "ddnm_op_mcsr_A_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                     c_void_p]),
+    "ddnm_op_mcsr_pinv_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                        c_void_p]),
+    "ddnm_step_mcsr_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                     c_int32, c_int32, c_int32, POINTER(c_float), POINTER(StepScalars), c_void_p]),
+    "ddnm_step_mcsr_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int32, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(StepScalars),
+                                           c_void_p]),
+    "ddnm_step_plus_mcsr_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float, c_float, c_float,
+                                          POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_mcsr_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float,
+                                                c_float, c_float, POINTER(StepScalars), c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ddnm_op_avgpool_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_op_upsample_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

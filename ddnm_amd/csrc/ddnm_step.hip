@@ -10,6 +10,7 @@
 //   inpainting        : A = gather kept, A^+ = scatter             (svd_operators.py:324-359)
 //   demosaicing       : A = one channel per pixel (CFA), A^+ = scatter   (the same class over single entries)
 //   denoising         : identity                                    (svd_operators.py:442-462)
+//   old photo (mcsr)  : A = pool . grey . mask, A^+ exact, one singular value per r x r site   (diffusion.py:260-290 has A)
 // Rounding follows the reference's evaluation order; contraction into FMA is disabled so
 // that mul/add round separately like the ATen elementwise kernels.
 #include "common.h"
@@ -1365,6 +1366,362 @@ extern "C" int ddnm_step_plus_cs_post_f32(const float* P, float* xt_next, int32_
     DDNM_LAUNCH(cs_plus_post_kernel, GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, P, xt_next, D, ps, total4);
     return 0;
 }
+
+// ---------------------------------------------------------------- fused: old photo (mask, grey, average pool)
+// A = pool_r . grey_w . mask (the Composition of the simplified path's mask_color_sr, guided_diffusion/diffusion.py:260-290)
+// with its exact pseudo-inverse.  Site j is an r x r block of the image, k_j the number of its kept pixels (m_p = 1):
+//   y_j = sum_c sum_{p in j} w_c m_p x[c][p] / r^2
+// The rows of A have disjoint supports, so A A^T is diagonal, U = I and row j = s_j q_j with
+//   s_j = sqrt(k_j) |w| / r^2,   q_j[c][p] = w_c m_p / (sqrt(k_j) |w|),   (A^+ y)[c][p] = m_p w_c r^2 y_j / (k_j |w|^2)
+// (k_j = 0: the site is null space, y_j is ignored).  With the unnormalised site sums S(v) = sum_c sum_p w_c m_p v[c][p],
+// q_j (q_j . v) = m_p (w_c / |w|^2) S(v) / k_j: no square root but the one of s_j, which only spectral_coef sees.
+//   DDNM  (svd_ddnm.py:57-65):   x0h = x0 - lambda m_p (w_c / |w|^2) (S(x0) - r^2 y_j) / k_j,  x_{t-1} = update_of(x0h, n, eps)
+//   DDNM+ (svd_ddnm.py:118-131), a = sqrt_at_next, (lambda_j, d1_j, d2_j) = spectral_coef(s_j), (1, d1n, d2n) = spectral_coef(0):
+//     x_{t-1} = a x0 + d1n n + d2n eps
+//               + m_p (w_c / |w|^2) [ -a lambda_j (S(x0) - r^2 y_j) + (d1_j - d1n) S(n) + (d2_j - d2n) S(eps) ] / k_j
+// eps enters as V^T eps and n is drawn in image space, as in step_plus_spectral_kernel.  Singular values differ inside one
+// launch: the coefficients are evaluated per site in the kernel, from the mask alone (no per-site table).
+// Mapping: one lane owns a strip of r rows x 4 pixels x 3 planes; it holds 4 / r whole sites for r = 1, 2, one for r = 4
+// and half a site for r = 8, where lanes 2i and 2i + 1 of the wave add their partial sums with one __shfl_xor (a + b is
+// the same number on both lanes, and a strip's sums do not depend on where its image stands in a batch).  Two passes per
+// strip: the site sums first, then xt, eps and the mask are read again (from L2) and the noise is drawn again from its
+// offset, so nothing of a strip stays in registers between them.  THE OUTPUTS MUST NOT ALIAS xt OR eps.
+// mask: a device plane [H*W] of 0 / 1 shared by all images, NULL = everything kept (sr_color: no mask is loaded).
+struct McsrW { float w[3], wp[3], wn; };   // w, w / |w|^2, |w|
+
+// DDNM_E_BADARG for weights that are all zero
+static int mcsr_weights(const float* w3_host, McsrW* out) {
+    McsrW c;
+    for (int i = 0; i < 3; ++i) c.w[i] = w3_host[i];
+    const float n2 = (c.w[0] * c.w[0] + c.w[1] * c.w[1]) + c.w[2] * c.w[2];
+    if (!(n2 > 0.f)) return DDNM_E_BADARG;
+    for (int i = 0; i < 3; ++i) c.wp[i] = c.w[i] / n2;
+    c.wn = sqrtf(n2);
+    *out = c;
+    return 0;
+}
+
+// sizes of every mcsr entry point, after its pointer checks (DDNM_E_BADARG before DDNM_E_SHAPE)
+static int mcsr_shape(int32_t H, int32_t W, int32_t r, int64_t et_bstride) {
+    if (r != 1 && r != 2 && r != 4 && r != 8) return DDNM_E_SHAPE;
+    if (H <= 0 || W <= 0 || H % r || W % r || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    return 0;
+}
+
+// a strip of R rows x 4 pixels: its sites (NS of them) and the geometry shared by the four kernels
+template <int R>
+struct McsrStrip {
+    static constexpr int NS = R >= 4 ? 1 : 4 / R;                         // whole sites of a strip (R = 8: half of one)
+    static __device__ __forceinline__ int site(int j) { return R >= 4 ? 0 : j / R; }   // site of column j of the strip
+    int64_t b, pix, ysite;   // image, offset of the strip's first row inside a plane, index of its first site in y
+    __device__ __forceinline__ McsrStrip(int64_t i, int H, int W) {
+        const int W4 = W >> 2;
+        const int64_t per_img = (int64_t)(H / R) * W4;
+        b = i / per_img;
+        const int64_t q = i - b * per_img;
+        const int sy = (int)(q / W4), xg = (int)(q - (int64_t)sy * W4);
+        pix = (int64_t)sy * R * W + xg * 4;
+        ysite = (b * (H / R) + sy) * (W / R) + (R >= 4 ? xg * 4 / R : xg * NS);
+    }
+};
+
+// the other half of a site's sum (R = 8: the neighbouring lane's strip); the strips of a site are i and i ^ 1 and their
+// number is even, so both lanes are in the loop together
+template <int R>
+__device__ __forceinline__ float mcsr_site_sum(float v) { return R == 8 ? v + __shfl_xor(v, 1) : v; }
+
+__device__ __forceinline__ f32x4 mcsr_mask4(const float* mask, int64_t off) {
+    return mask ? ld4(mask + off) : f32x4{1.f, 1.f, 1.f, 1.f};
+}
+
+// y = A x
+template <int R>
+__global__ __launch_bounds__(256) void mcsr_A_kernel(const float* __restrict__ x, const float* __restrict__ mask,
+                                                     float* __restrict__ y, int H, int W, int64_t total, McsrW cw) {
+    using S = McsrStrip<R>;
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const float* xb = x + t.b * 3 * hw + t.pix;
+        float sx[S::NS] = {};
+#pragma unroll
+        for (int row = 0; row < R; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 g = ((ld4(xb + o) * cw.w[0] + ld4(xb + hw + o) * cw.w[1]) + ld4(xb + 2 * hw + o) * cw.w[2]) *
+                            mcsr_mask4(mask, t.pix + o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sx[S::site(j)] += g[j];
+        }
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            const float v = mcsr_site_sum<R>(sx[k]) / (float)(R * R);
+            if (R < 8 || !(i & 1)) y[t.ysite + k] = v;
+        }
+    }
+}
+
+// x = A^+ y
+template <int R>
+__global__ __launch_bounds__(256) void mcsr_pinv_kernel(const float* __restrict__ y, const float* __restrict__ mask,
+                                                        float* __restrict__ x, int H, int W, int64_t total, McsrW cw) {
+    using S = McsrStrip<R>;
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        float kept[S::NS] = {};
+#pragma unroll
+        for (int row = 0; row < R; ++row) {
+            const f32x4 m = mcsr_mask4(mask, t.pix + (int64_t)row * W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) kept[S::site(j)] += m[j];
+        }
+        float g[S::NS];
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            const float kj = mcsr_site_sum<R>(kept[k]);
+            g[k] = kj > 0.f ? y[t.ysite + k] * (float)(R * R) / kj : 0.f;
+        }
+        f32x4 gv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = g[S::site(j)];
+        float* xb = x + t.b * 3 * hw + t.pix;
+#pragma unroll
+        for (int row = 0; row < R; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 mg = mcsr_mask4(mask, t.pix + o) * gv;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) st4(xb + c * hw + o, mg * cw.wp[c]);
+        }
+    }
+}
+
+template <int R, class NZ>
+__global__ __launch_bounds__(256) void step_mcsr_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                        int64_t et_bstride, NZ noise, const float* __restrict__ y,
+                                                        const float* __restrict__ mask, float* __restrict__ x0o,
+                                                        float* __restrict__ xn, int H, int W, int64_t total,
+                                                        ddnm_step_scalars s, McsrW cw) {
+    using S = McsrStrip<R>;
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const auto nz = bind(noise, t.b);
+        const int64_t base = t.b * 3 * hw + t.pix, ebase = t.b * et_bstride + t.pix;
+        float kept[S::NS] = {}, sx[S::NS] = {};
+#pragma unroll 1
+        for (int row = 0; row < R; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 m = mcsr_mask4(mask, t.pix + o);
+            f32x4 x0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x0[c] = x0_of(ld4(xt + base + c * hw + o), ld4(et + ebase + c * hw + o), s);
+            const f32x4 g = ((x0[0] * cw.w[0] + x0[1] * cw.w[1]) + x0[2] * cw.w[2]) * m;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { kept[S::site(j)] += m[j]; sx[S::site(j)] += g[j]; }
+        }
+        float g[S::NS];
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            const float kj = mcsr_site_sum<R>(kept[k]), sxj = mcsr_site_sum<R>(sx[k]);
+            g[k] = kj > 0.f ? (sxj - y[t.ysite + k] * (float)(R * R)) / kj * s.lambda : 0.f;
+        }
+        f32x4 gv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = g[S::site(j)];
+#pragma unroll 1
+        for (int row = 0; row < R; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 mg = mcsr_mask4(mask, t.pix + o) * gv;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 e = ld4(et + ebase + c * hw + o);
+                const f32x4 x0 = x0_of(ld4(xt + base + c * hw + o), e, s);
+                if (x0o) st4(x0o + base + c * hw + o, x0);
+                st4(xn + base + c * hw + o, update_of(x0 - mg * cw.wp[c], nz4(nz, base + c * hw + o), e, s));
+            }
+        }
+    }
+}
+
+template <int R, class NZ>
+__global__ __launch_bounds__(256) void step_plus_mcsr_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                             int64_t et_bstride, NZ noise, const float* __restrict__ y,
+                                                             const float* __restrict__ mask, float* __restrict__ x0o,
+                                                             float* __restrict__ xn, int H, int W, int64_t total,
+                                                             ddnm_step_scalars s, McsrW cw, float sy, float st, float eta,
+                                                             float eta_c) {
+    using S = McsrStrip<R>;
+    const int64_t hw = (int64_t)H * W;
+    const float a = s.sqrt_at_next;
+    const bool active = a != 0.f && sy != 0.f;
+    const SpectralCoef null = spectral_coef(0.f, active, a, sy, st, eta, eta_c);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const auto nz = bind(noise, t.b);
+        const int64_t base = t.b * 3 * hw + t.pix, ebase = t.b * et_bstride + t.pix;
+        float kept[S::NS] = {}, sx[S::NS] = {}, sn[S::NS] = {}, se[S::NS] = {};
+#pragma unroll 1
+        for (int row = 0; row < R; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 m = mcsr_mask4(mask, t.pix + o);
+            f32x4 x0[3], e[3], n[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                e[c] = ld4(et + ebase + c * hw + o);
+                x0[c] = x0_of(ld4(xt + base + c * hw + o), e[c], s);
+                n[c] = nz4(nz, base + c * hw + o);
+            }
+            const f32x4 gx = ((x0[0] * cw.w[0] + x0[1] * cw.w[1]) + x0[2] * cw.w[2]) * m;
+            const f32x4 gn = ((n[0] * cw.w[0] + n[1] * cw.w[1]) + n[2] * cw.w[2]) * m;
+            const f32x4 ge = ((e[0] * cw.w[0] + e[1] * cw.w[1]) + e[2] * cw.w[2]) * m;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                kept[S::site(j)] += m[j]; sx[S::site(j)] += gx[j]; sn[S::site(j)] += gn[j]; se[S::site(j)] += ge[j];
+            }
+        }
+        float g[S::NS];
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            const float kj = mcsr_site_sum<R>(kept[k]), sxj = mcsr_site_sum<R>(sx[k]);
+            const float snj = mcsr_site_sum<R>(sn[k]), sej = mcsr_site_sum<R>(se[k]);
+            g[k] = 0.f;
+            if (kj > 0.f) {
+                const SpectralCoef cf = spectral_coef(sqrtf(kj) * cw.wn / (float)(R * R), active, a, sy, st, eta, eta_c);
+                const float corr = (sxj - y[t.ysite + k] * (float)(R * R)) * (a * cf.lam);
+                g[k] = ((snj * (cf.d1 - null.d1) + sej * (cf.d2 - null.d2)) - corr) / kj;
+            }
+        }
+        f32x4 gv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = g[S::site(j)];
+#pragma unroll 1
+        for (int row = 0; row < R; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 mg = mcsr_mask4(mask, t.pix + o) * gv;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 e = ld4(et + ebase + c * hw + o);
+                const f32x4 x0 = x0_of(ld4(xt + base + c * hw + o), e, s);
+                st4(x0o + base + c * hw + o, x0);
+                const f32x4 n = nz4(nz, base + c * hw + o);
+                st4(xn + base + c * hw + o, ((x0 * a + n * null.d1) + e * null.d2) + mg * cw.wp[c]);
+            }
+        }
+    }
+}
+
+// strips of a launch: B images x H / r bands x W / 4 column groups (even for r = 8, where W % 8 == 0)
+static inline int64_t mcsr_strips(int32_t B, int32_t H, int32_t W, int32_t r) { return (int64_t)B * (H / r) * (W / 4); }
+
+#define MCSR_FOR_R(r, LAUNCH)        \
+    switch (r) {                     \
+    case 1: LAUNCH(1); break;        \
+    case 2: LAUNCH(2); break;        \
+    case 4: LAUNCH(4); break;        \
+    default: LAUNCH(8); break;       \
+    }
+
+extern "C" int ddnm_op_mcsr_A_f32(const float* x, const float* mask, float* y, int32_t B, int32_t H, int32_t W, int32_t r,
+                                  const float* w3_host, void* stream) {
+    McsrW cw;
+    if (!x || !y || !w3_host || B <= 0) return DDNM_E_BADARG;
+    if (int e = mcsr_weights(w3_host, &cw)) return e;
+    if (int e = mcsr_shape(H, W, r, 0)) return e;
+    const int64_t total = mcsr_strips(B, H, W, r);
+#define LAUNCH(R) DDNM_LAUNCH(mcsr_A_kernel<R>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, x, mask, y, H, W, total, cw)
+    MCSR_FOR_R(r, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+extern "C" int ddnm_op_mcsr_pinv_f32(const float* y, const float* mask, float* x, int32_t B, int32_t H, int32_t W, int32_t r,
+                                     const float* w3_host, void* stream) {
+    McsrW cw;
+    if (!x || !y || !w3_host || B <= 0) return DDNM_E_BADARG;
+    if (int e = mcsr_weights(w3_host, &cw)) return e;
+    if (int e = mcsr_shape(H, W, r, 0)) return e;
+    const int64_t total = mcsr_strips(B, H, W, r);
+#define LAUNCH(R) DDNM_LAUNCH(mcsr_pinv_kernel<R>, GRID_1D(total), dim3(256), 0, (hipStream_t)stream, y, mask, x, H, W, total, cw)
+    MCSR_FOR_R(r, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+// the pointer checks shared by the four step entry points (the noise source is the entry point's own)
+static inline bool mcsr_step_ptrs(const float* xt, const float* et, const float* y, const float* x0, const float* xt_next,
+                                  const float* w3_host, const ddnm_step_scalars* s, int32_t B) {
+    if (!xt || !et || !y || !xt_next || !w3_host || !s || B <= 0) return false;
+    // two passes: the outputs must not overlap the inputs.  Only identity is caught here; the rest is the caller's to keep.
+    return xt_next != xt && xt_next != et && xt_next != x0 && (!x0 || (x0 != xt && x0 != et));
+}
+
+template <class Src>
+static int launch_step_mcsr(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, const float* mask,
+                            float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t r, const float* w3_host,
+                            const ddnm_step_scalars* s, void* stream) {
+    McsrW cw;
+    if (int e = mcsr_weights(w3_host, &cw)) return e;
+    if (int e = mcsr_shape(H, W, r, et_bstride)) return e;
+    const int64_t total = mcsr_strips(B, H, W, r);
+#define LAUNCH(R)                                                                                                          \
+    DDNM_LAUNCH((step_mcsr_kernel<R, Src>), GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, mask, \
+                x0, xt_next, H, W, total, *s, cw)
+    MCSR_FOR_R(r, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+template <class Src>
+static int launch_step_plus_mcsr(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, const float* mask,
+                                 float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t r, const float* w3_host,
+                                 float sigma_y, float sigma_t, float eta, const ddnm_step_scalars* s, void* stream) {
+    McsrW cw;
+    if (int e = mcsr_weights(w3_host, &cw)) return e;
+    if (int e = mcsr_shape(H, W, r, et_bstride)) return e;
+    const int64_t total = mcsr_strips(B, H, W, r);
+    const float eta_c = (float)sqrt(1.0 - (double)eta * (double)eta);
+#define LAUNCH(R)                                                                                                          \
+    DDNM_LAUNCH((step_plus_mcsr_kernel<R, Src>), GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, y, \
+                mask, x0_out, xt_next, H, W, total, *s, cw, sigma_y, sigma_t, eta, eta_c)
+    MCSR_FOR_R(r, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+extern "C" int ddnm_step_mcsr_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                                  const float* mask, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t r,
+                                  const float* w3_host, const ddnm_step_scalars* s, void* stream) {
+    if (!mcsr_step_ptrs(xt, et, y, x0, xt_next, w3_host, s, B) || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_mcsr(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, mask, x0, xt_next, B, H, W, r, w3_host,
+                            s, stream);
+}
+
+extern "C" int ddnm_step_mcsr_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                        const float* y, const float* mask, float* x0, float* xt_next, int32_t B, int32_t H,
+                                        int32_t W, int32_t r, const float* w3_host, const ddnm_step_scalars* s, void* stream) {
+    if (!mcsr_step_ptrs(xt, et, y, x0, xt_next, w3_host, s, B) || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_mcsr(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, mask, x0, xt_next, B, H, W, r, w3_host,
+                            s, stream);
+}
+
+extern "C" int ddnm_step_plus_mcsr_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                       const float* y, const float* mask, float* x0_out, float* xt_next, int32_t B, int32_t H,
+                                       int32_t W, int32_t r, const float* w3_host, float sigma_y, float sigma_t, float eta,
+                                       const ddnm_step_scalars* s, void* stream) {
+    if (!x0_out || !mcsr_step_ptrs(xt, et, y, x0_out, xt_next, w3_host, s, B) || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_plus_mcsr(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, mask, x0_out, xt_next, B, H, W, r,
+                                 w3_host, sigma_y, sigma_t, eta, s, stream);
+}
+
+extern "C" int ddnm_step_plus_mcsr_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                             const float* y, const float* mask, float* x0_out, float* xt_next, int32_t B,
+                                             int32_t H, int32_t W, int32_t r, const float* w3_host, float sigma_y,
+                                             float sigma_t, float eta, const ddnm_step_scalars* s, void* stream) {
+    if (!x0_out || !mcsr_step_ptrs(xt, et, y, x0_out, xt_next, w3_host, s, B) || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_plus_mcsr(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, mask, x0_out, xt_next, B, H, W, r,
+                                 w3_host, sigma_y, sigma_t, eta, s, stream);
+}
+#undef MCSR_FOR_R
 
 
 // ---------------------------------------------------------------------------------------------

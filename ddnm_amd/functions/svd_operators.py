@@ -15,6 +15,9 @@ as one (or a few) hand-written HIP kernels:
                       holds one mask per run, so each image is checked against its single-mask operator
   Mosaic           -> demosaicing: that Inpainting over single entries, one colour sample per pixel behind a periodic
                       colour filter array; no table, y is a dense one-channel picture; `ddnm_plus_step` is ONE kernel
+  MaskColorSR      -> old photo: mask, grey, r x r mean in one operator with its exact A^+ (the simplified path's
+                      Composition has the same A but a chained inverse that is no pseudo-inverse where the mask cuts a
+                      site); one singular value per site, evaluated in the kernels; `ddnm_plus_step` is ONE kernel
   WalshHadamardCS  -> separable FWHT (shuffle + LDS) + permuted mask (svd_operators.py:211-251)
   Denoising        -> identity                                   (svd_operators.py:442-462)
 
@@ -1046,6 +1049,110 @@ def mask_color_sr(channels, img_dim, mask, scale, device):
                         SuperResolution(1, img_dim, int(scale), device)])
 
 
+MCSR_RATIOS = (1, 2, 4, 8)
+
+
+class MaskColorSR(A_functions):
+    """Old-photo restoration as ONE operator: mask, then grey, then `ratio` x `ratio` average pool -- the A of the
+    Composition above -- with its exact pseudo-inverse, for the DDNM and DDNM+ loops.  `mask` is a d x d array of 0 / 1
+    (1 = kept) or None (nothing masked: hq_demo's `sr_color`); `weights` are the grey weights, (1/3, 1/3, 1/3) by default.
+
+    The measurement rows have disjoint supports (row j: the kept pixels of site j, an r x r block, in the three planes),
+    so A A^T is diagonal, U = I, and with k_j kept pixels in site j
+        s_j = sqrt(k_j) |w| / r^2,   q_j[c][p] = w_c m_p / (sqrt(k_j) |w|),   (A^+ y)[c][p] = m_p w_c r^2 y_j / (k_j |w|^2);
+    a site with k_j = 0 is null space.  The chained inverse of the simplified path, mask . colour . upsample, gives
+    A A^+ y = (k_j / r^2) y on a site the mask cuts, so its "consistent" solution is not consistent around a scratch.
+    The kernels count k_j from the mask themselves (`*_mcsr_*`, csrc/ddnm_step.hip); `singulars()` is the s_j, one per
+    site.  `Lambda`, `Lambda_noise`, `V`, `Vt`, `U`, `Ut` stay NotImplementedError as for `SRConv`: they would need a
+    null-space basis and a spectral ordering of one's own invention; DDNM+ runs through the hook `ddnm_plus_step`, one launch
+    with the per-site coefficients evaluated in the kernel (singular values differ inside one launch)."""
+
+    def __init__(self, channels, img_dim, mask, ratio, device, weights=None):
+        if channels != 3:
+            raise ValueError(f"MaskColorSR turns RGB images grey: channels must be 3, got {channels}")
+        if ratio not in MCSR_RATIOS:
+            raise ValueError(f"MaskColorSR kernels pool by {', '.join(str(r) for r in MCSR_RATIOS)}: got ratio {ratio!r}")
+        if img_dim % ratio:
+            raise ValueError(f"img_dim must be a multiple of the pool ratio: {img_dim} % {ratio} != 0")
+        if img_dim % 4:
+            raise ValueError(f"MaskColorSR kernels handle four pixels of a row at once: img_dim must be a multiple of 4, got {img_dim}")
+        w = (1 / 3, 1 / 3, 1 / 3) if weights is None else tuple(float(v) for v in weights)
+        if len(w) != 3 or not any(np.float32(v) != 0 for v in w):
+            raise ValueError(f"MaskColorSR needs three grey weights that are not all zero, got {w}")
+        self.channels, self.img_dim, self.ratio, self.device = channels, img_dim, int(ratio), device
+        self.weights = w
+        self._w = (ctypes.c_float * 3)(*w)
+        if mask is None:
+            self.mask, m = None, np.ones((img_dim, img_dim), np.float32)
+        else:
+            m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+            if m.shape != (img_dim, img_dim):
+                raise ValueError(f"the mask of a {img_dim} x {img_dim} image is a 2-D array of that shape, got {m.shape}")
+            if not np.isin(m, (0, 1)).all():
+                raise ValueError("mask values are 0 (missing) and 1 (kept)")
+            m = np.ascontiguousarray(m, dtype=np.float32)
+            self.mask = torch.from_numpy(m).reshape(-1).to(device).contiguous()                # [HW], shared by the images
+        r, n = self.ratio, img_dim // self.ratio
+        self.kept = m.reshape(n, r, n, r).sum(axis=(1, 3)).reshape(-1).astype(np.int64)       # k_j per site, row-major
+        wn = float(np.sqrt(np.sum(np.asarray(self._w[:], dtype=np.float64) ** 2)))
+        self._singulars = torch.from_numpy((np.sqrt(self.kept) * wn / r ** 2).astype(np.float32)).to(device)
+
+    def measurement_size(self):
+        return (self.img_dim // self.ratio) ** 2
+
+    def measurement_image_shape(self):
+        return (1, self.img_dim // self.ratio, self.img_dim // self.ratio)
+
+    def singulars(self):
+        return self._singulars
+
+    def _geometry(self):
+        return self.img_dim, self.img_dim, self.ratio, self._w
+
+    def A(self, vec):
+        x = _img(vec, 3, self.img_dim)
+        B = x.shape[0]
+        y = torch.empty(B, self.measurement_size(), dtype=torch.float32, device=x.device)
+        ops.call("ddnm_op_mcsr_A_f32", _p(x), _p(self.mask), _p(y), B, *self._geometry())
+        return y
+
+    def A_pinv(self, vec):
+        y = _flat(vec)
+        B = y.shape[0]
+        if y.shape[1] != self.measurement_size():
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, this operator has {self.measurement_size()}")
+        x = torch.empty(B, 3 * self.img_dim ** 2, dtype=torch.float32, device=y.device)
+        ops.call("ddnm_op_mcsr_pinv_f32", _p(y), _p(self.mask), _p(x), B, *self._geometry())
+        return x
+
+    def _check_y(self, y, B):
+        if y.shape[0] != B or y.numel() != B * self.measurement_size():
+            raise ValueError(f"y must be [{B}, {self.measurement_size()}], got {tuple(y.shape)}")
+        return ops._f32c(y, "y")
+
+    def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
+        """x0_out (may be None) and xt_next must not alias xt or et: the kernel passes over a strip twice."""
+        B = xt.shape[0]
+        ops.step_call("ddnm_step_mcsr_f32", xt, et, noise, self._check_y(y, B), _p(self.mask), _p(x0_out), _p(xt_next), B,
+                      *self._geometry(), s)
+
+    # ---- DDNM+ (sigma_y > 0): the engine hook of `ddnm_plus_diffusion`
+    def begin_plus_run(self, y):
+        y = _flat(y)
+        self._plus_run = (y.shape[0], self._check_y(y, y.shape[0]))
+
+    def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
+        """One DDNM+ reverse step in one launch: x0|t into `x0_out` (uncorrected), x_{t-1} into `xt_next`, neither of them
+        xt or et; `et` may be the [:, :3] view of a 6-channel network output."""
+        B, d = xt.shape[0], self.img_dim
+        y, = _plus_state(self, B)
+        for name, t in (("xt", xt), ("x0_out", x0_out), ("xt_next", xt_next)):
+            if ops._f32c(t, name).numel() != 3 * B * d * d:
+                raise ValueError(f"ddnm_plus_step: {name} has {t.numel()} entries, expected {3 * B * d * d}")
+        ops.step_call("ddnm_step_plus_mcsr_f32", xt, et, noise, y, _p(self.mask), _p(x0_out), _p(xt_next), B,
+                      *self._geometry(), float(sigma_y), float(sigma_t), float(eta), s)
+
+
 class GeneralA(A_functions):
     """svd_operators.py:173-208: an explicit dense measurement matrix A [m, d] with a full LAPACK SVD (torch.svd on the
     host, like the reference's constructor; singular values below 1e-3 are zeroed, :184-185).  Used by none of the `--deg`
@@ -1454,6 +1561,14 @@ def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask
         return Deblurring2D(k1 / k1.sum(), k2 / k2.sum(), c, d, device)
     if deg == "cs_blockbased":
         return CS(c, d, deg_scale, device)                   # diffusion.py:459-462
+    if deg == "mask_color_sr":                               # old photo: masked, grey, small (deg_scale 1: masked colorization)
+        mask = np.load(mask_path)
+        if mask.ndim != 2:
+            raise ValueError(f"{mask_path}: --deg mask_color_sr takes one 2-D mask, got {mask.ndim}-D (banks of masks, one "
+                             "per image, are an inpainting feature)")
+        return MaskColorSR(c, d, mask, round(deg_scale), device)
+    if deg == "sr_color":                                    # hq_demo's name: grey and small, nothing masked
+        return MaskColorSR(c, d, None, round(deg_scale), device)
     raise ValueError("degradation type not supported")
 
 

@@ -39,7 +39,12 @@ Deliberate differences at the boundary (not in the results):
   * `--deg demosaic_rggb | demosaic_bggr | demosaic_grbg | demosaic_gbrg | demosaic_xtrans` (and `--deg demosaic` with
     the pattern of `exp/cfa/pattern.npy`) restores a raw sensor frame, one colour sample per pixel (svd_operators.Mosaic):
     the reference's Inpainting over single entries, so every switch above applies; its measurement is a one-channel
-    S x S picture, and `Apy_{i}.png` shows the coloured mosaic.
+    S x S picture, and `Apy_{i}.png` shows the coloured mosaic;
+  * `--deg mask_color_sr` (the 2-D mask of `exp/inp_masks/mask.npy`, grey, average pool by `--deg_scale` 1 | 2 | 4 | 8) and
+    `--deg sr_color` (the same without a mask) restore an old photo on the SVD path too (svd_operators.MaskColorSR: the
+    exact pseudo-inverse, one fused step kernel for DDNM and one for DDNM+), so every switch above applies; the measurement
+    is a one-channel S/r x S/r picture and `Apy_{i}.png` shows A^+ y.  `--simplified --deg mask_color_sr | diy` keeps the
+    reference's Composition and its chained inverse.
 
 All of these run through ONE path of `Diffusion.svd_based_ddnm_plus`: the plan (`fuse_groups`: which loader batches this
 rank restores, grouped into sampler calls; `restored_images` is the same plan as image indices), `prepare` (a loader batch

@@ -31,7 +31,7 @@ extern "C" {
 int ddnm_version(void);                 /* ABI version, currently 7 (bumped on every struct / prototype change; the
                                            per-image inpainting entry points *_pi_* were added under 7: new symbols
                                            only, no struct and no existing prototype changed; the demosaicing entry
-                                           points *_mosaic_* likewise) */
+                                           points *_mosaic_* and the old-photo ones *_mcsr_* likewise) */
 const char* ddnm_build_digest(void);    /* sha256 of the sources + flags this binary was built from (build.py) */
 int ddnm_sizeof(int which);             /* sizeof of 0: ddnm_conv_desc, 1: ddnm_gemm_desc, 2: ddnm_conv16_desc,
                                            3: ddnm_step_scalars as compiled into the binary (-1: unknown index) */
@@ -729,6 +729,60 @@ int ddnm_step_plus_mosaic_keyed_f32(const float* xt, const float* et, int64_t et
                                     const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
                                     const uint8_t* pattern_host, int32_t ph, int32_t pw, float a_lambda, float d1n,
                                     float d2n, float dd1, float dd2, const ddnm_step_scalars* s, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Old-photo restoration: mask, then grey, then r x r average pool in ONE operator -- the A of the simplified path's
+ * mask_color_sr (guided_diffusion/diffusion.py:260-290) with its exact pseudo-inverse (the reference chains
+ * mask . colour . upsample there, which is no pseudo-inverse on a site the mask cuts).  Added under ABI 7: new symbols only.
+ * Site j is an r x r block, k_j the number of its kept pixels (mask 1), |w|^2 = sum_c w_c^2:
+ *   y_j          = sum_c sum_{p in j} w_c m_p x[c][p] / r^2
+ *   s_j          = sqrt(k_j) |w| / r^2                  (k_j = 0: s_j = 0, the site is null space and y_j is ignored)
+ *   q_j[c][p]    = w_c m_p / (sqrt(k_j) |w|)            (the rows of A have disjoint supports: A A^T is diagonal, U = I)
+ *   (A^+ y)[c][p] = m_p w_c r^2 y_j / (k_j |w|^2)       (0 on sites with k_j = 0)
+ *   x [B][3][H][W], y [B][H/r][W/r], et row b at et + b*et_bstride (the [:, :3] view of a 6-channel output).
+ *   mask:    device plane [H*W] of 0 / 1 floats shared by all images; NULL = everything kept (sr_color; nothing is loaded).
+ *   w3_host: HOST pointer to the three grey weights, copied by value into the kernel arguments (required).
+ * The kernels count k_j from the mask and derive s_j and q_j themselves: no per-site table exists.  One lane owns a
+ * strip of r rows x 4 pixels x 3 planes; at r = 8 two neighbouring lanes add their halves of a site (one shuffle, fixed
+ * order), so an image gives the same bits alone and inside any batch.
+ * NULL pointer (mask, and x0 of the noise-free step, aside), B <= 0, no noise source, a misaligned key table, w all zero, or
+ * an output that is xt, et or the other output: DDNM_E_BADARG; then r not in {1, 2, 4, 8}, H or W <= 0, H % r, W % r, W % 4
+ * or et_bstride % 4 != 0: DDNM_E_SHAPE.  All of it is checked before any launch.
+ * ------------------------------------------------------------------------- */
+int ddnm_op_mcsr_A_f32(const float* x, const float* mask, float* y, int32_t B, int32_t H, int32_t W, int32_t r,
+                       const float* w3_host, void* stream);
+int ddnm_op_mcsr_pinv_f32(const float* y, const float* mask, float* x, int32_t B, int32_t H, int32_t W, int32_t r,
+                          const float* w3_host, void* stream);
+/* Fused noise-free step (functions/svd_ddnm.py:57-65):
+ *   x0 = (xt - et * sqrt_1m_at) / sqrt_at;   x0h = x0 - lambda * A^+(A x0 - y);   xt' = sqrt_at_next * x0h + c1 * noise + c2 * et.
+ * x0 (optional) receives the uncorrected x0, bit for bit that of ddnm_step_x0_f32; noise as in ddnm_step_mosaic_f32 /
+ * _keyed_f32.  TWO passes over a strip (site sums, then the update; the second reads xt, et and the mask again and draws
+ * the noise again from its offset): x0 and xt_next MUST NOT overlap xt or et.  That is the caller's obligation; only
+ * identity is checked (an output whose address equals xt, et or the other output: DDNM_E_BADARG), partly overlapping
+ * buffers are not detected. */
+int ddnm_step_mcsr_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                       const float* mask, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t r,
+                       const float* w3_host, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_mcsr_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys, const float* y,
+                             const float* mask, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t r,
+                             const float* w3_host, const ddnm_step_scalars* s, void* stream);
+/* The whole DDNM+ step (functions/svd_ddnm.py:80-164, step :118-131) in ONE launch, in the form of
+ * ddnm_step_plus_spectral_f32 (eps enters as V^T eps, n ~ N(0, I) is drawn in image space).  With a = s->sqrt_at_next,
+ * (lambda_j, d1_j, d2_j) the spectral coefficients of s_j -- evaluated per site in the kernel: one launch holds sites on
+ * both sides of the threshold sigma_t <> a sigma_y / s_j and null-space sites -- and (1, d1n, d2n) those of 0,
+ *   x0      = (xt - et * sqrt_1m_at) / sqrt_at                        -> x0_out, uncorrected (required)
+ *   x_{t-1} = a x0 + d1n n + d2n et
+ *             + q_j [ -a lambda_j (q_j . x0 - y_j / s_j) + (d1_j - d1n) (q_j . n) + (d2_j - d2n) (q_j . et) ]   where k_j > 0
+ * Two passes like the noise-free step: x0_out and xt_next must not overlap xt or et (checked for identity only, as there);
+ * the in-kernel and keyed noise sources are drawn once per pass, a noise tensor is read twice. */
+int ddnm_step_plus_mcsr_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                            const float* mask, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t r,
+                            const float* w3_host, float sigma_y, float sigma_t, float eta, const ddnm_step_scalars* s,
+                            void* stream);
+int ddnm_step_plus_mcsr_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                  const float* y, const float* mask, float* x0_out, float* xt_next, int32_t B, int32_t H,
+                                  int32_t W, int32_t r, const float* w3_host, float sigma_y, float sigma_t, float eta,
+                                  const ddnm_step_scalars* s, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * hq_demo sampler: DDPM posterior step with the DDNM core and the mask-shift tiles
