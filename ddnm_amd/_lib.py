@@ -5,7 +5,7 @@ or a kernel returns an error, this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_uint8, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libddnm_hip.so")
@@ -264,6 +264,23 @@ PROTOTYPES = {
     "ddnm_step_plus_mcsr_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float,
                                                 c_float, c_float, POINTER(StepScalars), c_void_p]),
+    # chroma subsampling (full luma, chroma per rw x rh site): the 3 x 3 colour matrix is a HOST array of nine floats
+    "ddnm_chroma_constants": (c_int32, [POINTER(c_float), c_int32, c_int32, POINTER(c_double)]),
+    "ddnm_op_chroma_A_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                       c_void_p]),
+    "ddnm_op_chroma_pinv_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                          c_void_p]),
+    "ddnm_step_chroma_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                       c_int32, c_int32, c_int32, POINTER(c_float), POINTER(StepScalars), c_void_p]),
+    "ddnm_step_chroma_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                             c_int32, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(StepScalars),
+                                             c_void_p]),
+    "ddnm_step_plus_chroma_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                            c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float, c_float, c_float,
+                                            POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_chroma_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float,
+                                                  c_float, c_float, POINTER(StepScalars), c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ddnm_op_avgpool_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_op_upsample_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

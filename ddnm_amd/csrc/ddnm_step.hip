@@ -11,10 +11,13 @@
 //   demosaicing       : A = one channel per pixel (CFA), A^+ = scatter   (the same class over single entries)
 //   denoising         : identity                                    (svd_operators.py:442-462)
 //   old photo (mcsr)  : A = pool . grey . mask, A^+ exact, one singular value per r x r site   (diffusion.py:260-290 has A)
+//   chroma subsampling: A = full luma + chroma averaged per rw x rh site, A^+ exact, four singular values per launch
 // Rounding follows the reference's evaluation order; contraction into FMA is disabled so
 // that mul/add round separately like the ATen elementwise kernels.
 #include "common.h"
 #include "philox.h"
+#include <math.h>
+#include <string.h>
 #pragma clang fp contract(off)
 
 #define GRID_1D(n) dim3((unsigned)(((n) + 255) / 256 < 8192 ? ((n) + 255) / 256 : 8192))
@@ -1722,6 +1725,546 @@ extern "C" int ddnm_step_plus_mcsr_keyed_f32(const float* xt, const float* et, i
                                  w3_host, sigma_y, sigma_t, eta, s, stream);
 }
 #undef MCSR_FOR_R
+
+// ---------------------------------------------------------------- fused: chroma subsampling (Y'CbCr 4:2:0, 4:2:2, 4:1:1)
+// A = full-resolution luma, chroma averaged over sites of rw columns x rh rows (n = rw rh pixels).  M is an invertible
+// 3 x 3 colour matrix with rows w_Y, w_Cb, w_Cr (no offsets: the data are centred):
+//   Y[p] = w_Y . x[:, p],   Cb[site] = mean_{p in site} w_Cb . x[:, p],   Cr likewise;   y row = [ Y | Cb | Cr ] planes
+// Per site, with mu(v) the mean colour and v_p - mu(v) the deviation, A splits into
+//   AC: the n - 1 zero-mean patterns times colour; A sees only w^ = w_Y / |w_Y|, singular value |w_Y|; the two colour
+//       directions orthogonal to w^ are null space;
+//   DC: in orthonormal coordinates the 3 x 3 matrix D = diag(1, 1/sqrt n, 1/sqrt n) M = U_D S_D V_D^T.
+// A launch has four singular values, the same at every site.  With Ybar the site mean of Y and w+ = w_Y / |w_Y|^2,
+//   (A^+ y)[:, p] = w+ (Y_p - Ybar) + M^-1 (Ybar, Cb, Cr)^T
+//   DDNM  (svd_ddnm.py:57-65):   x0h = x0 - lambda A^+(A x0 - y),  x_{t-1} = update_of(x0h, n, eps)
+//   DDNM+ (svd_ddnm.py:118-131), a = sqrt_at_next, (lambda_a, d1_a, d2_a) the coefficients of |w_Y|, (Lambda, D1, D2)
+//   those of S_D (diagonal), (1, d1n, d2n) those of 0, t_p(g) = w^ . g_p:
+//     x_{t-1}[:, p] = a x0_p + d1n n_p + d2n eps_p
+//        + w^  [ -a lambda_a ((t_p(x0) - tbar(x0)) - (Y_p - Ybar) / |w_Y|) + (d1_a - d1n)(t_p(n) - tbar(n)) + (d2_a - d2n)(..eps) ]
+//        + V_D [ -a Lambda (V_D^T mu(x0) - S_D^-1 U_D^T z') + (D1 - d1n) V_D^T mu(n) + (D2 - d2n) V_D^T mu(eps) ],
+//     z' = (Ybar, Cb / sqrt n, Cr / sqrt n).  The launcher evaluates the four coefficient triples once, in double, and folds
+//     everything that is constant over a site into four 3 x 3 matrices (tbar(g) = w^ . mu(g) goes there too):
+//       site term = Qx mu(x0) + Qz (Ybar, Cb, Cr) + Qn mu(n) + Qe mu(eps),   pixel term = w^ (kx t_p(x0) + ky Y_p + kn t_p(n) + ke t_p(eps))
+//     so the kernel evaluates no coefficient and no square root.
+// Mapping as for mcsr: one lane owns a strip of rh rows x 4 pixels x 3 planes -- two sites for rw = 2, one for rw = 4, half a
+// site for rw = 8, where lanes 2i and 2i + 1 add their halves with one __shfl_xor.  Two passes per strip (site means, then
+// the update; xt, eps and Y are read again and the noise is drawn again): THE OUTPUTS MUST NOT ALIAS xt OR eps.
+// A measurement row has H W + 2 H W / n entries, which is no multiple of 4 when the number of sites is odd: then the rows of
+// the images after the first are not 16-byte aligned and Y is moved one float at a time (`yal` = 0, uniform per launch).
+struct ChromaC { float m[9], mi[9], wp[3]; };                       // M, M^-1, w+
+struct ChromaPlusC { float qx[9], qz[9], qn[9], qe[9], wh[3], kx, ky, kn, ke, a, d1n, d2n; };
+struct ChromaK { double mi[9], wp[3], wh[3], wn, U[9], S[3], V[9]; };   // ddnm_chroma_constants' 37 doubles, in this order
+
+static inline bool chroma_site_ok(int32_t rw, int32_t rh) {
+    return (rw == 2 && rh == 1) || (rw == 4 && rh == 1) || (rw == 2 && rh == 2) || (rw == 4 && rh == 4) || (rw == 8 && rh == 8);
+}
+
+// eigenvectors (columns of V) and eigenvalues of a symmetric 3 x 3 matrix by cyclic Jacobi rotations
+static void chroma_jacobi3(double G[3][3], double V[3][3], double ev[3]) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        const double off = G[0][1] * G[0][1] + G[0][2] * G[0][2] + G[1][2] * G[1][2];
+        const double tr = fabs(G[0][0]) + fabs(G[1][1]) + fabs(G[2][2]);
+        if (off <= 1e-40 * tr * tr) break;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                if (G[p][q] == 0.0) continue;
+                const double theta = (G[q][q] - G[p][p]) / (2.0 * G[p][q]);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 3; ++k) {
+                    const double gp = G[k][p], gq = G[k][q];
+                    G[k][p] = c * gp - s * gq;
+                    G[k][q] = s * gp + c * gq;
+                }
+                for (int k = 0; k < 3; ++k) {
+                    const double gp = G[p][k], gq = G[q][k];
+                    G[p][k] = c * gp - s * gq;
+                    G[q][k] = s * gp + c * gq;
+                }
+                for (int k = 0; k < 3; ++k) {
+                    const double vp = V[k][p], vq = V[k][q];
+                    V[k][p] = c * vp - s * vq;
+                    V[k][q] = s * vp + c * vq;
+                }
+            }
+    }
+    for (int i = 0; i < 3; ++i) ev[i] = G[i][i];
+}
+
+// What the launchers derive from M, in double (row-major 3 x 3; the columns of U and V are the singular vectors, S descends).
+// DDNM_E_BADARG: a null pointer or a singular M (|det M| < 1e-6 |M|_F^3); DDNM_E_SHAPE: an unsupported site.
+static int chroma_constants(const float* m9, int32_t rw, int32_t rh, ChromaK* out) {
+    if (!m9 || !out) return DDNM_E_BADARG;
+    double M[3][3], f2 = 0.0;
+    for (int i = 0; i < 9; ++i) { M[i / 3][i % 3] = (double)m9[i]; f2 += (double)m9[i] * (double)m9[i]; }
+    double C[3][3];                                                  // cofactors: M^-1 = C^T / det
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            C[i][j] = M[i1][j1] * M[i2][j2] - M[i1][j2] * M[i2][j1];
+        }
+    const double det = M[0][0] * C[0][0] + M[0][1] * C[0][1] + M[0][2] * C[0][2];
+    const double bound = 1e-6 * f2 * sqrt(f2);
+    if (!(f2 > 0.0) || !(fabs(det) >= bound)) return DDNM_E_BADARG;
+    if (!chroma_site_ok(rw, rh)) return DDNM_E_SHAPE;
+    ChromaK k;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) k.mi[i * 3 + j] = C[j][i] / det;
+    const double n2 = M[0][0] * M[0][0] + M[0][1] * M[0][1] + M[0][2] * M[0][2];
+    k.wn = sqrt(n2);
+    for (int j = 0; j < 3; ++j) { k.wp[j] = M[0][j] / n2; k.wh[j] = M[0][j] / k.wn; }
+    const double e[3] = {1.0, 1.0 / sqrt((double)(rw * rh)), 1.0 / sqrt((double)(rw * rh))};
+    double D[3][3], G[3][3], V[3][3], ev[3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) D[i][j] = e[i] * M[i][j];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) G[i][j] = D[0][i] * D[0][j] + D[1][i] * D[1][j] + D[2][i] * D[2][j];
+    chroma_jacobi3(G, V, ev);
+    int ord[3] = {0, 1, 2};
+    for (int i = 0; i < 2; ++i)
+        for (int j = i + 1; j < 3; ++j)
+            if (ev[ord[j]] > ev[ord[i]]) { const int t = ord[i]; ord[i] = ord[j]; ord[j] = t; }
+    for (int c = 0; c < 3; ++c) {
+        const int o = ord[c];
+        if (!(ev[o] > 0.0)) return DDNM_E_BADARG;
+        k.S[c] = sqrt(ev[o]);
+        for (int i = 0; i < 3; ++i) k.V[i * 3 + c] = V[i][o];
+        for (int i = 0; i < 3; ++i) k.U[i * 3 + c] = (D[i][0] * V[0][o] + D[i][1] * V[1][o] + D[i][2] * V[2][o]) / k.S[c];
+    }
+    *out = k;
+    return 0;
+}
+
+extern "C" int ddnm_chroma_constants(const float* m9_host, int32_t rw, int32_t rh, double* out) {
+    ChromaK k;
+    if (!out) return DDNM_E_BADARG;
+    if (int e = chroma_constants(m9_host, rw, rh, &k)) return e;
+    memcpy(out, &k, sizeof k);
+    return 0;
+}
+
+// (lambda, d1, d2) of one singular value in double: the rules of spectral_coef above
+static void chroma_coef(double s, double a, double sy, double st, double eta, double out[3]) {
+    const double c1 = st * eta, c2 = st * sqrt(1.0 - eta * eta);
+    out[0] = 1.0; out[1] = c1; out[2] = c2;
+    if (s == 0.0 || a == 0.0 || sy == 0.0) return;
+    const double thr = a * sy / s;
+    if (st < thr) { out[0] = s * st * sqrt(1.0 - eta * eta) / a / sy; out[2] = 0.0; }
+    if (st > thr) { out[1] = sqrt(st * st - a * a * sy * sy / (s * s)); out[2] = 0.0; }
+}
+
+static ChromaC chroma_args(const float* m9, const ChromaK& k) {
+    ChromaC c;
+    for (int i = 0; i < 9; ++i) { c.m[i] = m9[i]; c.mi[i] = (float)k.mi[i]; }
+    for (int i = 0; i < 3; ++i) c.wp[i] = (float)k.wp[i];
+    return c;
+}
+
+// the per-launch constants of the DDNM+ step: four coefficient triples, folded into the site matrices and pixel factors
+static ChromaPlusC chroma_plus_args(const ChromaK& k, int32_t rw, int32_t rh, double a, double sy, double st, double eta) {
+    double ca[3], cn[3], cd[3][3];
+    chroma_coef(k.wn, a, sy, st, eta, ca);
+    chroma_coef(0.0, a, sy, st, eta, cn);
+    for (int c = 0; c < 3; ++c) chroma_coef(k.S[c], a, sy, st, eta, cd[c]);
+    const double e[3] = {1.0, 1.0 / sqrt((double)(rw * rh)), 1.0 / sqrt((double)(rw * rh))};
+    ChromaPlusC p;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double qx = 0.0, qz = 0.0, qn = 0.0, qe = 0.0;
+            for (int c = 0; c < 3; ++c) {
+                const double vi = k.V[i * 3 + c], vj = k.V[j * 3 + c];
+                qx -= vi * a * cd[c][0] * vj;
+                qz += vi * a * cd[c][0] / k.S[c] * k.U[j * 3 + c] * e[j];
+                qn += vi * (cd[c][1] - cn[1]) * vj;
+                qe += vi * (cd[c][2] - cn[2]) * vj;
+            }
+            const double ww = k.wh[i] * k.wh[j];
+            p.qx[i * 3 + j] = (float)(qx + a * ca[0] * ww);
+            p.qz[i * 3 + j] = (float)(qz - (j == 0 ? a * ca[0] / k.wn * k.wh[i] : 0.0));
+            p.qn[i * 3 + j] = (float)(qn - (ca[1] - cn[1]) * ww);
+            p.qe[i * 3 + j] = (float)(qe - (ca[2] - cn[2]) * ww);
+        }
+    for (int i = 0; i < 3; ++i) p.wh[i] = (float)k.wh[i];
+    p.kx = (float)(-a * ca[0]);
+    p.ky = (float)(a * ca[0] / k.wn);
+    p.kn = (float)(ca[1] - cn[1]);
+    p.ke = (float)(ca[2] - cn[2]);
+    p.a = (float)a; p.d1n = (float)cn[1]; p.d2n = (float)cn[2];
+    return p;
+}
+
+// sizes of every chroma entry point, after its pointer checks (DDNM_E_BADARG before DDNM_E_SHAPE)
+static int chroma_shape(int32_t H, int32_t W, int32_t rw, int32_t rh, int64_t et_bstride) {
+    if (!chroma_site_ok(rw, rh)) return DDNM_E_SHAPE;
+    if (H <= 0 || W <= 0 || H % rh || W % rw || (W & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    return 0;
+}
+
+// a strip of RH rows x 4 pixels: its sites (NS of them) and the geometry shared by the four kernels
+template <int RW, int RH>
+struct ChromaStrip {
+    static constexpr int NS = RW == 2 ? 2 : 1;                            // whole sites of a strip (RW = 8: half of one)
+    static constexpr int N = RW * RH;
+    static __device__ __forceinline__ int site(int j) { return RW == 2 ? j / 2 : 0; }   // site of column j of the strip
+    int64_t b, pix, csite;   // image, offset of the strip's first row inside a plane, index of its first site in a chroma plane
+    __device__ __forceinline__ ChromaStrip(int64_t i, int H, int W) {
+        const int W4 = W >> 2;
+        const int64_t per_img = (int64_t)(H / RH) * W4;
+        b = i / per_img;
+        const int64_t q = i - b * per_img;
+        const int sy = (int)(q / W4), xg = (int)(q - (int64_t)sy * W4);
+        pix = (int64_t)sy * RH * W + xg * 4;
+        csite = (int64_t)sy * (W / RW) + xg * 4 / RW;
+    }
+};
+
+// the other half of a site's sum (RW = 8: the neighbouring lane's strip); the strips of a site are i and i ^ 1 and their
+// number per row is even, so both lanes are in the loop together
+template <int RW>
+__device__ __forceinline__ float chroma_site_sum(float v) { return RW == 8 ? v + __shfl_xor(v, 1) : v; }
+
+__device__ __forceinline__ f32x4 chroma_ldy(const float* p, bool al) { return al ? ld4(p) : f32x4{p[0], p[1], p[2], p[3]}; }
+__device__ __forceinline__ void chroma_sty(float* p, f32x4 v, bool al) {
+    if (al) { st4(p, v); return; }
+    p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3];
+}
+__device__ __forceinline__ f32x4 dot3(const float* w, f32x4 r, f32x4 g, f32x4 b) { return (r * w[0] + g * w[1]) + b * w[2]; }
+__device__ __forceinline__ float dot3(const float* w, float r, float g, float b) { return (r * w[0] + g * w[1]) + b * w[2]; }
+
+// y = A x
+template <int RW, int RH>
+__global__ __launch_bounds__(256) void chroma_A_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W,
+                                                       int64_t total, bool yal, ChromaC cc) {
+    using S = ChromaStrip<RW, RH>;
+    const int64_t hw = (int64_t)H * W, hwn = hw / S::N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const float* xb = x + t.b * 3 * hw + t.pix;
+        float* yb = y + t.b * (hw + 2 * hwn);
+        float sb[S::NS] = {}, sr[S::NS] = {};
+#pragma unroll
+        for (int row = 0; row < RH; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 r = ld4(xb + o), g = ld4(xb + hw + o), b = ld4(xb + 2 * hw + o);
+            chroma_sty(yb + t.pix + o, dot3(cc.m, r, g, b), yal);
+            const f32x4 cb = dot3(cc.m + 3, r, g, b), cr = dot3(cc.m + 6, r, g, b);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sb[S::site(j)] += cb[j]; sr[S::site(j)] += cr[j]; }
+        }
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            const float vb = chroma_site_sum<RW>(sb[k]) / (float)S::N, vr = chroma_site_sum<RW>(sr[k]) / (float)S::N;
+            if (RW < 8 || !(i & 1)) { yb[hw + t.csite + k] = vb; yb[hw + hwn + t.csite + k] = vr; }
+        }
+    }
+}
+
+// x = A^+ y
+template <int RW, int RH>
+__global__ __launch_bounds__(256) void chroma_pinv_kernel(const float* __restrict__ y, float* __restrict__ x, int H, int W,
+                                                          int64_t total, bool yal, ChromaC cc) {
+    using S = ChromaStrip<RW, RH>;
+    const int64_t hw = (int64_t)H * W, hwn = hw / S::N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const float* yb = y + t.b * (hw + 2 * hwn);
+        float sy[S::NS] = {};
+#pragma unroll
+        for (int row = 0; row < RH; ++row) {
+            const f32x4 yp = chroma_ldy(yb + t.pix + (int64_t)row * W, yal);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sy[S::site(j)] += yp[j];
+        }
+        float ym[S::NS], dc[3][S::NS];
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            ym[k] = chroma_site_sum<RW>(sy[k]) / (float)S::N;
+            const float cb = yb[hw + t.csite + k], cr = yb[hw + hwn + t.csite + k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dc[c][k] = dot3(cc.mi + 3 * c, ym[k], cb, cr);
+        }
+        f32x4 ymv, dcv[3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            ymv[j] = ym[S::site(j)];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dcv[c][j] = dc[c][S::site(j)];
+        }
+        float* xb = x + t.b * 3 * hw + t.pix;
+#pragma unroll
+        for (int row = 0; row < RH; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 d = chroma_ldy(yb + t.pix + o, yal) - ymv;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) st4(xb + c * hw + o, d * cc.wp[c] + dcv[c]);
+        }
+    }
+}
+
+template <int RW, int RH, class NZ>
+__global__ __launch_bounds__(256) void step_chroma_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                          int64_t et_bstride, NZ noise, const float* __restrict__ y,
+                                                          float* __restrict__ x0o, float* __restrict__ xn, int H, int W,
+                                                          int64_t total, bool yal, ddnm_step_scalars s, ChromaC cc) {
+    using S = ChromaStrip<RW, RH>;
+    const int64_t hw = (int64_t)H * W, hwn = hw / S::N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const auto nz = bind(noise, t.b);
+        const int64_t base = t.b * 3 * hw + t.pix, ebase = t.b * et_bstride + t.pix;
+        const float* yb = y + t.b * (hw + 2 * hwn);
+        // pass 1: the site means of the residual A x0 - y (luma, Cb, Cr)
+        float sy[S::NS] = {}, sb[S::NS] = {}, sr[S::NS] = {};
+#pragma unroll 1
+        for (int row = 0; row < RH; ++row) {
+            const int64_t o = (int64_t)row * W;
+            f32x4 x0[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x0[c] = x0_of(ld4(xt + base + c * hw + o), ld4(et + ebase + c * hw + o), s);
+            const f32x4 ry = dot3(cc.m, x0[0], x0[1], x0[2]) - chroma_ldy(yb + t.pix + o, yal);
+            const f32x4 cb = dot3(cc.m + 3, x0[0], x0[1], x0[2]), cr = dot3(cc.m + 6, x0[0], x0[1], x0[2]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sy[S::site(j)] += ry[j]; sb[S::site(j)] += cb[j]; sr[S::site(j)] += cr[j]; }
+        }
+        float rm[S::NS], dc[3][S::NS];
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            rm[k] = chroma_site_sum<RW>(sy[k]) / (float)S::N;
+            const float rb = chroma_site_sum<RW>(sb[k]) / (float)S::N - yb[hw + t.csite + k];
+            const float rr = chroma_site_sum<RW>(sr[k]) / (float)S::N - yb[hw + hwn + t.csite + k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dc[c][k] = dot3(cc.mi + 3 * c, rm[k], rb, rr) * s.lambda;
+        }
+        f32x4 rmv, dcv[3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            rmv[j] = rm[S::site(j)];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dcv[c][j] = dc[c][S::site(j)];
+        }
+        // pass 2: x0h = x0 - lambda (w+ (r_p - rbar) + M^-1 (rbar, rCb, rCr)), then the update
+#pragma unroll 1
+        for (int row = 0; row < RH; ++row) {
+            const int64_t o = (int64_t)row * W;
+            f32x4 x0[3], e[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                e[c] = ld4(et + ebase + c * hw + o);
+                x0[c] = x0_of(ld4(xt + base + c * hw + o), e[c], s);
+            }
+            const f32x4 g = ((dot3(cc.m, x0[0], x0[1], x0[2]) - chroma_ldy(yb + t.pix + o, yal)) - rmv) * s.lambda;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (x0o) st4(x0o + base + c * hw + o, x0[c]);
+                st4(xn + base + c * hw + o, update_of(x0[c] - (g * cc.wp[c] + dcv[c]), nz4(nz, base + c * hw + o), e[c], s));
+            }
+        }
+    }
+}
+
+template <int RW, int RH, class NZ>
+__global__ __launch_bounds__(256) void step_plus_chroma_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                               int64_t et_bstride, NZ noise, const float* __restrict__ y,
+                                                               float* __restrict__ x0o, float* __restrict__ xn, int H, int W,
+                                                               int64_t total, bool yal, ddnm_step_scalars s, ChromaPlusC cp) {
+    using S = ChromaStrip<RW, RH>;
+    const int64_t hw = (int64_t)H * W, hwn = hw / S::N;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const S t(i, H, W);
+        const auto nz = bind(noise, t.b);
+        const int64_t base = t.b * 3 * hw + t.pix, ebase = t.b * et_bstride + t.pix;
+        const float* yb = y + t.b * (hw + 2 * hwn);
+        // pass 1: the site sums of x0, n, eps per colour and of Y
+        float sx[3][S::NS] = {}, sn[3][S::NS] = {}, se[3][S::NS] = {}, sy[S::NS] = {};
+#pragma unroll 1
+        for (int row = 0; row < RH; ++row) {
+            const int64_t o = (int64_t)row * W;
+            const f32x4 yp = chroma_ldy(yb + t.pix + o, yal);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sy[S::site(j)] += yp[j];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const f32x4 e = ld4(et + ebase + c * hw + o);
+                const f32x4 x0 = x0_of(ld4(xt + base + c * hw + o), e, s);
+                const f32x4 n = nz4(nz, base + c * hw + o);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { sx[c][S::site(j)] += x0[j]; sn[c][S::site(j)] += n[j]; se[c][S::site(j)] += e[j]; }
+            }
+        }
+        float dc[3][S::NS];
+#pragma unroll
+        for (int k = 0; k < S::NS; ++k) {
+            float mx[3], mn[3], me[3], z[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                mx[c] = chroma_site_sum<RW>(sx[c][k]) / (float)S::N;
+                mn[c] = chroma_site_sum<RW>(sn[c][k]) / (float)S::N;
+                me[c] = chroma_site_sum<RW>(se[c][k]) / (float)S::N;
+            }
+            z[0] = chroma_site_sum<RW>(sy[k]) / (float)S::N;
+            z[1] = yb[hw + t.csite + k];
+            z[2] = yb[hw + hwn + t.csite + k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                dc[c][k] = (dot3(cp.qx + 3 * c, mx[0], mx[1], mx[2]) + dot3(cp.qz + 3 * c, z[0], z[1], z[2])) +
+                           (dot3(cp.qn + 3 * c, mn[0], mn[1], mn[2]) + dot3(cp.qe + 3 * c, me[0], me[1], me[2]));
+        }
+        f32x4 dcv[3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dcv[c][j] = dc[c][S::site(j)];
+        // pass 2: the pixel term along w^, the site term, the update
+#pragma unroll 1
+        for (int row = 0; row < RH; ++row) {
+            const int64_t o = (int64_t)row * W;
+            f32x4 x0[3], e[3], n[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                e[c] = ld4(et + ebase + c * hw + o);
+                x0[c] = x0_of(ld4(xt + base + c * hw + o), e[c], s);
+                n[c] = nz4(nz, base + c * hw + o);
+            }
+            const f32x4 tp = (dot3(cp.wh, x0[0], x0[1], x0[2]) * cp.kx + chroma_ldy(yb + t.pix + o, yal) * cp.ky) +
+                             (dot3(cp.wh, n[0], n[1], n[2]) * cp.kn + dot3(cp.wh, e[0], e[1], e[2]) * cp.ke);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                st4(x0o + base + c * hw + o, x0[c]);
+                st4(xn + base + c * hw + o, ((x0[c] * cp.a + n[c] * cp.d1n) + e[c] * cp.d2n) + (tp * cp.wh[c] + dcv[c]));
+            }
+        }
+    }
+}
+
+// strips of a launch: B images x H / rh bands x W / 4 column groups (even per row for rw = 8, where W % 8 == 0)
+static inline int64_t chroma_strips(int32_t B, int32_t H, int32_t W, int32_t rh) { return (int64_t)B * (H / rh) * (W / 4); }
+// whether every image's measurement row starts 16-byte aligned (given that y does)
+static inline bool chroma_y_aligned(int32_t H, int32_t W, int32_t rw, int32_t rh) {
+    return (((int64_t)H * W + 2 * ((int64_t)H * W / (rw * rh))) & 3) == 0;
+}
+
+#define CHROMA_FOR_SITE(rw, rh, LAUNCH)           \
+    switch (rw * 16 + rh) {                       \
+    case 2 * 16 + 1: LAUNCH(2, 1); break;         \
+    case 4 * 16 + 1: LAUNCH(4, 1); break;         \
+    case 2 * 16 + 2: LAUNCH(2, 2); break;         \
+    case 4 * 16 + 4: LAUNCH(4, 4); break;         \
+    default: LAUNCH(8, 8); break;                 \
+    }
+
+extern "C" int ddnm_op_chroma_A_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                                    const float* m9_host, void* stream) {
+    ChromaK k;
+    if (!x || !y || !m9_host || B <= 0) return DDNM_E_BADARG;
+    if (int e = chroma_constants(m9_host, rw, rh, &k)) return e;        // a singular M (DDNM_E_BADARG) before the site
+    if (int e = chroma_shape(H, W, rw, rh, 0)) return e;
+    const ChromaC cc = chroma_args(m9_host, k);
+    const int64_t total = chroma_strips(B, H, W, rh);
+    const bool yal = chroma_y_aligned(H, W, rw, rh);
+#define LAUNCH(RW, RH) \
+    DDNM_LAUNCH((chroma_A_kernel<RW, RH>), GRID_1D(total), dim3(256), 0, (hipStream_t)stream, x, y, H, W, total, yal, cc)
+    CHROMA_FOR_SITE(rw, rh, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+extern "C" int ddnm_op_chroma_pinv_f32(const float* y, float* x, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                                       const float* m9_host, void* stream) {
+    ChromaK k;
+    if (!x || !y || !m9_host || B <= 0) return DDNM_E_BADARG;
+    if (int e = chroma_constants(m9_host, rw, rh, &k)) return e;
+    if (int e = chroma_shape(H, W, rw, rh, 0)) return e;
+    const ChromaC cc = chroma_args(m9_host, k);
+    const int64_t total = chroma_strips(B, H, W, rh);
+    const bool yal = chroma_y_aligned(H, W, rw, rh);
+#define LAUNCH(RW, RH) \
+    DDNM_LAUNCH((chroma_pinv_kernel<RW, RH>), GRID_1D(total), dim3(256), 0, (hipStream_t)stream, y, x, H, W, total, yal, cc)
+    CHROMA_FOR_SITE(rw, rh, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+// the pointer checks shared by the four step entry points (the noise source is the entry point's own)
+static inline bool chroma_step_ptrs(const float* xt, const float* et, const float* y, const float* x0, const float* xt_next,
+                                    const float* m9_host, const ddnm_step_scalars* s, int32_t B) {
+    if (!xt || !et || !y || !xt_next || !m9_host || !s || B <= 0) return false;
+    // two passes: the outputs must not overlap the inputs.  Only identity is caught here; the rest is the caller's to keep.
+    return xt_next != xt && xt_next != et && xt_next != x0 && (!x0 || (x0 != xt && x0 != et));
+}
+
+template <class Src>
+static int launch_step_chroma(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0,
+                              float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh, const float* m9_host,
+                              const ddnm_step_scalars* s, void* stream) {
+    ChromaK k;
+    if (int e = chroma_constants(m9_host, rw, rh, &k)) return e;
+    if (int e = chroma_shape(H, W, rw, rh, et_bstride)) return e;
+    const ChromaC cc = chroma_args(m9_host, k);
+    const int64_t total = chroma_strips(B, H, W, rh);
+    const bool yal = chroma_y_aligned(H, W, rw, rh);
+#define LAUNCH(RW, RH)                                                                                                     \
+    DDNM_LAUNCH((step_chroma_kernel<RW, RH, Src>), GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, src, \
+                y, x0, xt_next, H, W, total, yal, *s, cc)
+    CHROMA_FOR_SITE(rw, rh, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+template <class Src>
+static int launch_step_plus_chroma(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0_out,
+                                   float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                                   const float* m9_host, float sigma_y, float sigma_t, float eta, const ddnm_step_scalars* s,
+                                   void* stream) {
+    ChromaK k;
+    if (int e = chroma_constants(m9_host, rw, rh, &k)) return e;
+    if (int e = chroma_shape(H, W, rw, rh, et_bstride)) return e;
+    const ChromaPlusC cp = chroma_plus_args(k, rw, rh, (double)s->sqrt_at_next, (double)sigma_y, (double)sigma_t, (double)eta);
+    const int64_t total = chroma_strips(B, H, W, rh);
+    const bool yal = chroma_y_aligned(H, W, rw, rh);
+#define LAUNCH(RW, RH)                                                                                                     \
+    DDNM_LAUNCH((step_plus_chroma_kernel<RW, RH, Src>), GRID_1D(total), dim3(256), 0, (hipStream_t)stream, xt, et, et_bstride, \
+                src, y, x0_out, xt_next, H, W, total, yal, *s, cp)
+    CHROMA_FOR_SITE(rw, rh, LAUNCH)
+#undef LAUNCH
+    return 0;
+}
+
+extern "C" int ddnm_step_chroma_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                                    float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                                    const float* m9_host, const ddnm_step_scalars* s, void* stream) {
+    if (!chroma_step_ptrs(xt, et, y, x0, xt_next, m9_host, s, B) || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_chroma(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, x0, xt_next, B, H, W, rw, rh,
+                              m9_host, s, stream);
+}
+
+extern "C" int ddnm_step_chroma_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                          const float* y, float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw,
+                                          int32_t rh, const float* m9_host, const ddnm_step_scalars* s, void* stream) {
+    if (!chroma_step_ptrs(xt, et, y, x0, xt_next, m9_host, s, B) || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_chroma(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, x0, xt_next, B, H, W, rw, rh,
+                              m9_host, s, stream);
+}
+
+extern "C" int ddnm_step_plus_chroma_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                         const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                         int32_t rw, int32_t rh, const float* m9_host, float sigma_y, float sigma_t, float eta,
+                                         const ddnm_step_scalars* s, void* stream) {
+    if (!x0_out || !chroma_step_ptrs(xt, et, y, x0_out, xt_next, m9_host, s, B) || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_plus_chroma(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, x0_out, xt_next, B, H, W, rw,
+                                   rh, m9_host, sigma_y, sigma_t, eta, s, stream);
+}
+
+extern "C" int ddnm_step_plus_chroma_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                               const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                               int32_t rw, int32_t rh, const float* m9_host, float sigma_y, float sigma_t,
+                                               float eta, const ddnm_step_scalars* s, void* stream) {
+    if (!x0_out || !chroma_step_ptrs(xt, et, y, x0_out, xt_next, m9_host, s, B) || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_plus_chroma(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, x0_out, xt_next, B, H, W, rw,
+                                   rh, m9_host, sigma_y, sigma_t, eta, s, stream);
+}
+#undef CHROMA_FOR_SITE
 
 
 // ---------------------------------------------------------------------------------------------

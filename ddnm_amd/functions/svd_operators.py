@@ -18,6 +18,9 @@ as one (or a few) hand-written HIP kernels:
   MaskColorSR      -> old photo: mask, grey, r x r mean in one operator with its exact A^+ (the simplified path's
                       Composition has the same A but a chained inverse that is no pseudo-inverse where the mask cuts a
                       site); one singular value per site, evaluated in the kernels; `ddnm_plus_step` is ONE kernel
+  ChromaSubsample  -> Y'CbCr 4:2:0 / 4:2:2 / 4:1:1: full-resolution luma, chroma averaged per rw x rh site, with the exact
+                      A^+ = w+ (Y - Ybar) + M^-1 (Ybar, Cb, Cr); four singular values per launch (|w_Y| and the 3 x 3 SVD of
+                      the site means), evaluated on the host; `ddnm_plus_step` is ONE kernel
   WalshHadamardCS  -> separable FWHT (shuffle + LDS) + permuted mask (svd_operators.py:211-251)
   Denoising        -> identity                                   (svd_operators.py:442-462)
 
@@ -1153,6 +1156,108 @@ class MaskColorSR(A_functions):
                       *self._geometry(), float(sigma_y), float(sigma_t), float(eta), s)
 
 
+BT601 = ((0.299, 0.587, 0.114), (-0.168736, -0.331264, 0.5), (0.5, -0.418688, -0.081312))      # full range, rows w_Y, w_Cb, w_Cr
+CHROMA_SITES = ((2, 1), (4, 1), (2, 2), (4, 4), (8, 8))                                         # (rw, rh): columns x rows
+CHROMA_NAMES = {"chroma_420": (2, 2), "chroma_422": (2, 1), "chroma_411": (4, 1)}
+CHROMA_SQUARE = (2, 4, 8)
+
+
+class ChromaSubsample(A_functions):
+    """Chroma subsampling as JPEG and the video codecs store it: luma Y = w_Y . x at every pixel, the chroma planes
+    Cb = w_Cb . x and Cr = w_Cr . x averaged over sites of `rw` columns x `rh` rows (n = rw rh).  `matrix` is an invertible
+    3 x 3 colour matrix with rows w_Y, w_Cb, w_Cr (no offsets: the data are centred), full-range BT.601 by default.  A
+    measurement row is [ Y | Cb | Cr ], each plane row-major: d^2 + 2 d^2 / n entries.
+
+    Per site, with mu(v) the mean colour: the n - 1 zero-mean patterns are seen through w^ = w_Y / |w_Y| alone (singular
+    value |w_Y|; the two colour directions orthogonal to w^ are null space) and the mean through the 3 x 3 matrix
+    D = diag(1, 1/sqrt n, 1/sqrt n) M = U_D S_D V_D^T.  So there are four singular values, the same at every site, A has
+    full row rank, and with Ybar the site mean of Y and w+ = w_Y / |w_Y|^2
+        (A^+ y)[:, p] = w+ (Y_p - Ybar) + M^-1 (Ybar, Cb, Cr)^T.
+    The entry points (`*_chroma_*`, csrc/ddnm_step.hip) derive all of this from the nine matrix entries on the host
+    (`ddnm_chroma_constants`).  `Lambda`, `Lambda_noise`, `V`, `Vt`, `U`, `Ut` stay NotImplementedError as for `MaskColorSR`;
+    DDNM+ runs through the hook `ddnm_plus_step`, one launch with the four coefficient triples evaluated per launch."""
+
+    def __init__(self, channels, img_dim, rw, rh, device, matrix=None):
+        if channels != 3:
+            raise ValueError(f"ChromaSubsample splits RGB images into luma and chroma: channels must be 3, got {channels}")
+        if (rw, rh) not in CHROMA_SITES:
+            raise ValueError(f"ChromaSubsample kernels have the sites (rw, rh) {', '.join(str(v) for v in CHROMA_SITES)}: "
+                             f"got {(rw, rh)!r}")
+        if img_dim % rw or img_dim % rh:
+            raise ValueError(f"img_dim must be a multiple of the site: {img_dim} % {rw} or {img_dim} % {rh} != 0")
+        if img_dim % 4:
+            raise ValueError(f"ChromaSubsample kernels handle four pixels of a row at once: img_dim must be a multiple of 4, got {img_dim}")
+        m = np.asarray(BT601 if matrix is None else matrix, dtype=np.float32)
+        if m.shape != (3, 3):
+            raise ValueError(f"the colour matrix is 3 x 3 (rows w_Y, w_Cb, w_Cr), got shape {m.shape}")
+        m64 = m.astype(np.float64)                                  # what the entry points see: fp32 entries, algebra in double
+        if not np.isfinite(m64).all() or not abs(np.linalg.det(m64)) >= 1e-6 * np.linalg.norm(m64) ** 3 or not m64.any():
+            raise ValueError(f"the colour matrix must be invertible (|det| >= 1e-6 |M|_F^3), got det {np.linalg.det(m64):.3e}")
+        self.channels, self.img_dim, self.rw, self.rh, self.device = channels, img_dim, int(rw), int(rh), device
+        self.matrix = m64
+        self._m = (ctypes.c_float * 9)(*[float(v) for v in m.reshape(-1)])
+        n, sites = self.rw * self.rh, img_dim ** 2 // (self.rw * self.rh)
+        self.wn = float(np.sqrt((m64[0] ** 2).sum()))
+        self.dc_singulars = np.linalg.svd(np.diag([1.0, n ** -0.5, n ** -0.5]) @ m64, compute_uv=False)
+        spectrum = np.concatenate([np.full(sites * (n - 1), self.wn)] + [np.full(sites, v) for v in self.dc_singulars])
+        self._singulars = torch.from_numpy(np.sort(spectrum)[::-1].astype(np.float32)).to(device)
+
+    def measurement_size(self):
+        return self.img_dim ** 2 + 2 * (self.img_dim ** 2 // (self.rw * self.rh))
+
+    def measurement_image_shape(self):
+        return None                                                  # three planes of two sizes: measurements are .npy rows
+
+    def singulars(self):
+        return self._singulars
+
+    def _geometry(self):
+        return self.img_dim, self.img_dim, self.rw, self.rh, self._m
+
+    def A(self, vec):
+        x = _img(vec, 3, self.img_dim)
+        B = x.shape[0]
+        y = torch.empty(B, self.measurement_size(), dtype=torch.float32, device=x.device)
+        ops.call("ddnm_op_chroma_A_f32", _p(x), _p(y), B, *self._geometry())
+        return y
+
+    def A_pinv(self, vec):
+        y = _flat(vec)
+        B = y.shape[0]
+        if y.shape[1] != self.measurement_size():
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, this operator has {self.measurement_size()}")
+        x = torch.empty(B, 3 * self.img_dim ** 2, dtype=torch.float32, device=y.device)
+        ops.call("ddnm_op_chroma_pinv_f32", _p(y), _p(x), B, *self._geometry())
+        return x
+
+    def _check_y(self, y, B):
+        if y.shape[0] != B or y.numel() != B * self.measurement_size():
+            raise ValueError(f"y must be [{B}, {self.measurement_size()}], got {tuple(y.shape)}")
+        return ops._f32c(y, "y")
+
+    def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
+        """x0_out (may be None) and xt_next must not alias xt or et: the kernel passes over a strip twice."""
+        B = xt.shape[0]
+        ops.step_call("ddnm_step_chroma_f32", xt, et, noise, self._check_y(y, B), _p(x0_out), _p(xt_next), B,
+                      *self._geometry(), s)
+
+    # ---- DDNM+ (sigma_y > 0): the engine hook of `ddnm_plus_diffusion`
+    def begin_plus_run(self, y):
+        y = _flat(y)
+        self._plus_run = (y.shape[0], self._check_y(y, y.shape[0]))
+
+    def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
+        """One DDNM+ reverse step in one launch: x0|t into `x0_out` (uncorrected), x_{t-1} into `xt_next`, neither of them
+        xt or et; `et` may be the [:, :3] view of a 6-channel network output."""
+        B, d = xt.shape[0], self.img_dim
+        y, = _plus_state(self, B)
+        for name, t in (("xt", xt), ("x0_out", x0_out), ("xt_next", xt_next)):
+            if ops._f32c(t, name).numel() != 3 * B * d * d:
+                raise ValueError(f"ddnm_plus_step: {name} has {t.numel()} entries, expected {3 * B * d * d}")
+        ops.step_call("ddnm_step_plus_chroma_f32", xt, et, noise, y, _p(x0_out), _p(xt_next), B, *self._geometry(),
+                      float(sigma_y), float(sigma_t), float(eta), s)
+
+
 class GeneralA(A_functions):
     """svd_operators.py:173-208: an explicit dense measurement matrix A [m, d] with a full LAPACK SVD (torch.svd on the
     host, like the reference's constructor; singular values below 1e-3 are zeroed, :184-185).  Used by none of the `--deg`
@@ -1569,6 +1674,13 @@ def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask
         return MaskColorSR(c, d, mask, round(deg_scale), device)
     if deg == "sr_color":                                    # hq_demo's name: grey and small, nothing masked
         return MaskColorSR(c, d, None, round(deg_scale), device)
+    if deg in CHROMA_NAMES:                                  # 4:2:0, 4:2:2, 4:1:1; --deg_scale is not read
+        return ChromaSubsample(c, d, *CHROMA_NAMES[deg], device)
+    if deg == "chroma_sub":                                  # square sites of --deg_scale 2 | 4 | 8
+        if deg_scale not in CHROMA_SQUARE:
+            raise ValueError(f"--deg chroma_sub takes --deg_scale {' | '.join(str(r) for r in CHROMA_SQUARE)} (square chroma "
+                             f"sites), got {deg_scale!r}")
+        return ChromaSubsample(c, d, int(deg_scale), int(deg_scale), device)
     raise ValueError("degradation type not supported")
 
 

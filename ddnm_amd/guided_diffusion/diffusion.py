@@ -44,7 +44,12 @@ Deliberate differences at the boundary (not in the results):
     `--deg sr_color` (the same without a mask) restore an old photo on the SVD path too (svd_operators.MaskColorSR: the
     exact pseudo-inverse, one fused step kernel for DDNM and one for DDNM+), so every switch above applies; the measurement
     is a one-channel S/r x S/r picture and `Apy_{i}.png` shows A^+ y.  `--simplified --deg mask_color_sr | diy` keeps the
-    reference's Composition and its chained inverse.
+    reference's Composition and its chained inverse;
+  * `--deg chroma_420 | chroma_422 | chroma_411` (chroma sites of 2 x 2, 2 x 1, 4 x 1 pixels; `--deg_scale` is not read) and
+    `--deg chroma_sub --deg_scale 2 | 4 | 8` (square sites) restore a picture stored as Y'CbCr with subsampled chroma:
+    full-resolution luma, one Cb and one Cr sample per site (svd_operators.ChromaSubsample, full-range BT.601: the exact
+    pseudo-inverse, one fused step kernel for DDNM and one for DDNM+), so every switch above applies; a measurement is the
+    three planes in a row, S^2 + 2 S^2 / n values, which no picture holds (`.npy` rows), and `Apy_{i}.png` shows A^+ y.
 
 All of these run through ONE path of `Diffusion.svd_based_ddnm_plus`: the plan (`fuse_groups`: which loader batches this
 rank restores, grouped into sampler calls; `restored_images` is the same plan as image indices), `prepare` (a loader batch

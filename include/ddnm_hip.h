@@ -31,7 +31,8 @@ extern "C" {
 int ddnm_version(void);                 /* ABI version, currently 7 (bumped on every struct / prototype change; the
                                            per-image inpainting entry points *_pi_* were added under 7: new symbols
                                            only, no struct and no existing prototype changed; the demosaicing entry
-                                           points *_mosaic_* and the old-photo ones *_mcsr_* likewise) */
+                                           points *_mosaic_*, the old-photo ones *_mcsr_* and the chroma ones
+                                           *_chroma_* likewise) */
 const char* ddnm_build_digest(void);    /* sha256 of the sources + flags this binary was built from (build.py) */
 int ddnm_sizeof(int which);             /* sizeof of 0: ddnm_conv_desc, 1: ddnm_gemm_desc, 2: ddnm_conv16_desc,
                                            3: ddnm_step_scalars as compiled into the binary (-1: unknown index) */
@@ -783,6 +784,70 @@ int ddnm_step_plus_mcsr_keyed_f32(const float* xt, const float* et, int64_t et_b
                                   const float* y, const float* mask, float* x0_out, float* xt_next, int32_t B, int32_t H,
                                   int32_t W, int32_t r, const float* w3_host, float sigma_y, float sigma_t, float eta,
                                   const ddnm_step_scalars* s, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Chroma-subsampled restoration (Y'CbCr 4:2:0, 4:2:2, 4:1:1): full-resolution luma, chroma averaged over sites of
+ * rw columns x rh rows (n = rw rh), with the exact pseudo-inverse.  The reference has no such operator; the entry points
+ * stand for A / A_pinv of its operator classes in the steps of functions/svd_ddnm.py:57-65 (DDNM) and :80-164 (DDNM+).
+ * Added under ABI 7: new symbols only.
+ *   M = m9_host: HOST pointer to a 3 x 3 colour matrix, row-major, rows w_Y, w_Cb, w_Cr, invertible (required); no offsets,
+ *       the data are centred.  Full-range BT.601: (0.299, 0.587, 0.114), (-0.168736, -0.331264, 0.5), (0.5, -0.418688, -0.081312).
+ *   Y[i][j]  = w_Y . x[:, i, j];   Cb[I][J] = (1/n) sum_{(i,j) in site(I,J)} w_Cb . x[:, i, j];   Cr likewise
+ *   x [B][3][H][W];  y [B][H W + 2 H W / n]: the planes Y [H][W], Cb [H/rh][W/rw], Cr [H/rh][W/rw], row-major each;
+ *   et row b at et + b*et_bstride (the [:, :3] view of a 6-channel output).
+ * Per site, with mu(v) the mean colour: the n - 1 zero-mean patterns see only w^ = w_Y / |w_Y| (singular value |w_Y|, the
+ * two colour directions orthogonal to w^ are null space), and the mean goes through D = diag(1, 1/sqrt n, 1/sqrt n) M =
+ * U_D S_D V_D^T.  A launch has four singular values, the same at every site; A has full row rank.  With Ybar the site
+ * mean of Y and w+ = w_Y / |w_Y|^2,
+ *   (A^+ y)[:, p] = w+ (Y_p - Ybar) + M^-1 (Ybar, Cb, Cr)^T.
+ * Sites (rw, rh): (2,1) 4:2:2, (4,1) 4:1:1, (2,2) 4:2:0, (4,4), (8,8).  One lane owns a strip of rh rows x 4 pixels x 3
+ * planes; at rw = 8 two neighbouring lanes add their halves of a site (one shuffle, fixed order), so an image gives the
+ * same bits alone and inside any batch.
+ * NULL pointer (x0 of the noise-free step aside), B <= 0, no noise source, a misaligned key table, an output that is xt, et
+ * or the other output, or a singular M (|det M| < 1e-6 |M|_F^3 in double): DDNM_E_BADARG; then a site not listed, H or
+ * W <= 0, H % rh, W % rw, W % 4 or et_bstride % 4 != 0: DDNM_E_SHAPE.  All of it is checked before any launch.
+ * ------------------------------------------------------------------------- */
+/* What the launchers derive from M, in double, host only (no device call): out[37] =
+ *   M^-1 [9], w+ [3], w^ [3], |w_Y| [1], U_D [9], S_D [3] (descending), V_D [9]
+ * (3 x 3 row-major; the COLUMNS of U_D and V_D are the singular vectors; a Jacobi iteration on D^T D, no library; the
+ * signs of a pair (u_k, v_k) are the iteration's).  A client supplies only M: the launchers call this themselves. */
+int ddnm_chroma_constants(const float* m9_host, int32_t rw, int32_t rh, double* out);
+int ddnm_op_chroma_A_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                         const float* m9_host, void* stream);
+int ddnm_op_chroma_pinv_f32(const float* y, float* x, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                            const float* m9_host, void* stream);
+/* Fused noise-free step (functions/svd_ddnm.py:57-65):
+ *   x0 = (xt - et * sqrt_1m_at) / sqrt_at;   x0h = x0 - lambda * A^+(A x0 - y);   xt' = sqrt_at_next * x0h + c1 * noise + c2 * et.
+ * x0 (optional) receives the uncorrected x0, bit for bit that of ddnm_step_x0_f32; noise as in ddnm_step_mcsr_f32 /
+ * _keyed_f32.  TWO passes over a strip (site means of the residual, then the update; the second reads xt, et and Y again
+ * and draws the noise again from its offset): x0 and xt_next MUST NOT overlap xt or et.  That is the caller's obligation;
+ * only identity is checked (DDNM_E_BADARG), partly overlapping buffers are not detected. */
+int ddnm_step_chroma_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y, float* x0,
+                         float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh, const float* m9_host,
+                         const ddnm_step_scalars* s, void* stream);
+int ddnm_step_chroma_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys, const float* y,
+                               float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                               const float* m9_host, const ddnm_step_scalars* s, void* stream);
+/* The whole DDNM+ step (functions/svd_ddnm.py:80-164, step :118-131) in ONE launch, in the form of
+ * ddnm_step_plus_spectral_f32 (eps enters as V^T eps, n ~ N(0, I) is drawn in image space).  With a = s->sqrt_at_next,
+ * (lambda_a, d1_a, d2_a) the spectral coefficients of |w_Y|, (Lambda, D1, D2) those of S_D (diagonal), (1, d1n, d2n)
+ * those of 0, t_p(g) = w^ . g_p with site mean tbar, z' = (Ybar, Cb / sqrt n, Cr / sqrt n):
+ *   x0      = (xt - et * sqrt_1m_at) / sqrt_at                        -> x0_out, uncorrected (required)
+ *   x_{t-1}[:, p] = a x0_p + d1n n_p + d2n et_p
+ *      + w^  [ -a lambda_a ((t_p(x0) - tbar(x0)) - (Y_p - Ybar) / |w_Y|) + (d1_a - d1n)(t_p(n) - tbar(n)) + (d2_a - d2n)(t_p(et) - tbar(et)) ]
+ *      + V_D [ -a Lambda (V_D^T mu(x0) - S_D^-1 U_D^T z') + (D1 - d1n) V_D^T mu(n) + (D2 - d2n) V_D^T mu(et) ]
+ * The launcher evaluates the four coefficient triples once per launch, in double, and passes what is constant over a site
+ * as four 3 x 3 matrices; the kernel evaluates no coefficient.  Two passes like the noise-free step: x0_out and xt_next
+ * must not overlap xt or et (checked for identity only); the in-kernel and keyed noise sources are drawn once per pass, a
+ * noise tensor is read twice. */
+int ddnm_step_plus_chroma_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                              float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                              const float* m9_host, float sigma_y, float sigma_t, float eta, const ddnm_step_scalars* s,
+                              void* stream);
+int ddnm_step_plus_chroma_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                    const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw,
+                                    int32_t rh, const float* m9_host, float sigma_y, float sigma_t, float eta,
+                                    const ddnm_step_scalars* s, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * hq_demo sampler: DDPM posterior step with the DDNM core and the mask-shift tiles

@@ -38,7 +38,7 @@ FLAGS = [
     (("--config",), dict(type=str, required=True, help="YAML under configs/ (or an absolute path)")),
     (("--seed",), dict(type=int, default=1234, help="seed of torch / numpy / the device generator")),
     (("--exp",), dict(type=str, default="exp", help="root of the run directory (<exp>/image_samples, <exp>/datasets, <exp>/logs)")),
-    (("--deg",), dict(type=str, required=True, help="degradation operator, e.g. sr_bicubic, colorization, inpainting, cs_walshhadamard, deblur_gauss, demosaic_rggb, mask_color_sr (old photo: exp/inp_masks/mask.npy, grey, --deg_scale 1 | 2 | 4 | 8), sr_color (the same without a mask)")),
+    (("--deg",), dict(type=str, required=True, help="degradation operator, e.g. sr_bicubic, colorization, inpainting, cs_walshhadamard, deblur_gauss, demosaic_rggb, mask_color_sr (old photo: exp/inp_masks/mask.npy, grey, --deg_scale 1 | 2 | 4 | 8), sr_color (the same without a mask), chroma_420 | chroma_422 | chroma_411 (full luma, subsampled chroma), chroma_sub (square chroma sites of --deg_scale 2 | 4 | 8)")),
     (("--path_y",), dict(type=str, required=True, help="dataset sub-folder below <exp>/datasets, synthetic:N, or measurements:DIR (given measurements, no ground truth)")),
     (("--sigma_y",), dict(type=float, default=0.0, help="std of the measurement noise on the [0,1] scale (> 0 selects DDNM+)")),
     (("--eta",), dict(type=float, default=0.85, help="eta of the DDIM-style update")),
