@@ -248,6 +248,21 @@ PROTOTYPES = {
     "ddnm_step_plus_mosaic_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_int32, c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, c_float,
                                                   c_float, c_float, c_float, c_float, POINTER(StepScalars), c_void_p]),
+    # DDNM+ with per-entry measurement noise: (sigma_map, sigma_mode, s2, g, sigma_t, sigma_t2, c1, c2) before the scalars
+    "ddnm_step_plus_mosaic_hn_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                               c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, c_void_p, c_int32,
+                                               c_float, c_float, c_float, c_float, c_float, c_float, POINTER(StepScalars),
+                                               c_void_p]),
+    "ddnm_step_plus_mosaic_hn_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_int32, c_int32, c_int32, POINTER(c_uint8), c_int32, c_int32, c_void_p,
+                                                     c_int32, c_float, c_float, c_float, c_float, c_float, c_float,
+                                                     POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_denoise_hn_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                                c_int64, c_void_p, c_int32, c_float, c_float, c_float, c_float, c_float,
+                                                c_float, POINTER(StepScalars), c_void_p]),
+    "ddnm_step_plus_denoise_hn_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_int32, c_int64, c_void_p, c_int32, c_float, c_float, c_float, c_float,
+                                                      c_float, c_float, POINTER(StepScalars), c_void_p]),
     # old photo (mask, grey, pool): the mask is a device plane (NULL = all kept), the three grey weights a HOST array
     "ddnm_op_mcsr_A_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
                                      c_void_p]),

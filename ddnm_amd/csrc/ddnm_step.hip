@@ -528,6 +528,202 @@ extern "C" int ddnm_step_denoise_f32(const float* xt, const float* et, int64_t e
     return launch_step_denoise(xt, et, et_bstride, noise_src(noise, s, chw), y, x0, xt_next, B, chw, s, stream);
 }
 
+// ---------------------------------------------------------------- fused DDNM+: per-entry measurement noise (mosaic, denoising)
+// The DDNM+ reverse step (functions/svd_ddnm.py:118-131) of the two operators whose U is the identity and whose measured
+// entries all have singular value 1 (svd_operators.py:361-439 over single entries, :442-476), with a DIAGONAL noise
+// covariance: entry j of y carries its own sigma_j, which is already diagonal in the operator's spectral basis, so the
+// rules of spectral_coefficients(1, ...) (the change_index masks of svd_operators.py:367-436) hold per entry.  With
+// a = sqrt_at_next, thr = a sigma_j and (st, st2, c1, c2) = (sigma_t, sigma_t^2, sigma_t eta, sigma_t sqrt(1 - eta^2)) of HnCoef:
+//   sigma_j == 0 or a == 0 : (a lambda, d1, d2) = (a, c1, c2)
+//   st < thr               : (a * (c2 / thr), c1, 0)
+//   st > thr               : (a, sqrt(st2 - thr * thr), 0)          (the difference is clamped at 0 before the root)
+//   st == thr              : (a, c1, c2)
+//   x_{t-1} = ((a x0 - a lambda (x0 - y)) + d1 n) + d2 eps          unmeasured entries: (0, c1, c2), i.e. a x0 + c1 n + c2 eps
+// The kernels are templates on the sigma source as they are on the noise source: SigmaMap loads sigma_j (engine scale,
+// [-1, 1]) with the float4 index of y inside the image -- one row, shared by the batch --; SigmaShot evaluates
+// sigma_j = 2 sqrt(s2 + g u_j), u_j = clamp((y_j + 1) / 2, 0, 1), from the y already in registers (s2, g on the [0, 1]
+// scale): no table, no extra bytes.
+struct SigmaMap { const float* p; };
+struct SigmaShot { float s2, g; };
+struct HnCoef { float st, st2, c1, c2; };
+
+__device__ __forceinline__ f32x4 sigma4(const SigmaMap& m, f32x4, int64_t off) { return ld4(m.p + off); }
+__device__ __forceinline__ f32x4 sigma4(const SigmaShot& m, f32x4 y, int64_t) {
+    f32x4 sg;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float u = (y[j] + 1.f) * 0.5f;
+        u = u < 0.f ? 0.f : (u > 1.f ? 1.f : u);
+        sg[j] = 2.f * sqrtf(m.s2 + m.g * u);
+    }
+    return sg;
+}
+
+// (a lambda, d1, d2) of four measured entries
+__device__ __forceinline__ void hn_coef4(f32x4 sg, float a, const HnCoef& k, f32x4& al, f32x4& d1, f32x4& d2) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float thr = a * sg[j];
+        al[j] = a, d1[j] = k.c1, d2[j] = k.c2;
+        if (sg[j] == 0.f || a == 0.f) continue;
+        if (k.st < thr) {
+            al[j] = a * (k.c2 / thr);
+            d2[j] = 0.f;
+        } else if (k.st > thr) {
+            const float v = k.st2 - thr * thr;
+            d1[j] = sqrtf(v > 0.f ? v : 0.f);
+            d2[j] = 0.f;
+        }
+    }
+}
+
+// the mosaic: step_plus_mosaic_kernel with the coefficients of the sampled entry evaluated per pixel -- 14 planes of HW
+// floats per image with in-kernel noise, one more (the row, once per image) for SigmaMap
+template <class NZ, class SG>
+__global__ __launch_bounds__(256) void step_plus_mosaic_hn_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                                  int64_t et_bstride, NZ noise, const float* __restrict__ y,
+                                                                  SG sigma, float* __restrict__ x0o, float* __restrict__ xn,
+                                                                  int W, int64_t hw4, int64_t total4, ddnm_step_scalars s,
+                                                                  Cfa cfa, HnCoef k) {
+    const float a = s.sqrt_at_next;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / hw4, p = i - b * hw4;
+        const auto nz = bind(noise, b);
+        const int64_t base = (b * 3 * hw4 + p) * 4, ebase = b * et_bstride + p * 4;
+        const f32x4 yv = ld4(y + i * 4);
+        f32x4 alm, d1m, d2m;
+        hn_coef4(sigma4(sigma, yv, p * 4), a, k, alm, d1m, d2m);
+        int code[4];
+        cfa_codes(cfa, p, W, code);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const f32x4 e = ld4(et + ebase + c * hw4 * 4);
+            const f32x4 x0 = x0_of(ld4(xt + base + c * hw4 * 4), e, s);
+            st4(x0o + base + c * hw4 * 4, x0);
+            const f32x4 n = nz4(nz, base + c * hw4 * 4);
+            f32x4 al, d1, d2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool m = code[j] == c;
+                al[j] = m ? alm[j] : 0.f;
+                d1[j] = m ? d1m[j] : k.c1;
+                d2[j] = m ? d2m[j] : k.c2;
+            }
+            st4(xn + base + c * hw4 * 4, ((x0 * a - (x0 - yv) * al) + n * d1) + e * d2);
+        }
+    }
+}
+
+// denoising (A = I): every entry is measured; y [B][chw], the row [chw]
+template <class NZ, class SG>
+__global__ __launch_bounds__(256) void step_plus_denoise_hn_kernel(const float* __restrict__ xt, const float* __restrict__ et,
+                                                                   int64_t et_bstride, NZ noise, const float* __restrict__ y,
+                                                                   SG sigma, float* __restrict__ x0o, float* __restrict__ xn,
+                                                                   int64_t chw4, int64_t total4, ddnm_step_scalars s, HnCoef k) {
+    const float a = s.sqrt_at_next;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / chw4, r = i - b * chw4;
+        const auto nz = bind(noise, b);
+        const f32x4 e = ld4(et + b * et_bstride + r * 4);
+        const f32x4 x0 = x0_of(ld4(xt + i * 4), e, s);
+        st4(x0o + i * 4, x0);
+        const f32x4 yv = ld4(y + i * 4);
+        f32x4 al, d1, d2;
+        hn_coef4(sigma4(sigma, yv, r * 4), a, k, al, d1, d2);
+        st4(xn + i * 4, ((x0 * a - (x0 - yv) * al) + nz4(nz, i * 4) * d1) + e * d2);
+    }
+}
+
+// The noise model of an *_hn_* entry point, after its pointer checks: sigma_mode 0 = the row `sigma_map`, 1 = shot + read.
+enum { DDNM_HN_MAP = 0, DDNM_HN_SHOT = 1 };
+static inline bool hn_ptrs(const float* sigma_map, int32_t sigma_mode) {      // the row is read 16 bytes at a time
+    return sigma_mode != DDNM_HN_MAP || (sigma_map != nullptr && (reinterpret_cast<uintptr_t>(sigma_map) & 15) == 0);
+}
+static inline bool hn_nonneg(float v) { return isfinite(v) && v >= 0.f; }
+static int hn_model(int32_t sigma_mode, float s2, float g, float sigma_t, float sigma_t2, float c1, float c2) {
+    if (sigma_mode != DDNM_HN_MAP && sigma_mode != DDNM_HN_SHOT) return DDNM_E_SHAPE;
+    if (sigma_mode == DDNM_HN_SHOT && (!hn_nonneg(s2) || !hn_nonneg(g))) return DDNM_E_SHAPE;
+    if (!hn_nonneg(sigma_t) || !hn_nonneg(sigma_t2) || !isfinite(c1) || !isfinite(c2)) return DDNM_E_SHAPE;
+    return 0;
+}
+
+template <class Src>
+static int launch_step_plus_mosaic_hn(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0_out,
+                                      float* xt_next, int32_t B, int32_t H, int32_t W, const uint8_t* pattern_host, int32_t ph,
+                                      int32_t pw, const float* sigma_map, int32_t sigma_mode, float s2, float g, HnCoef k,
+                                      const ddnm_step_scalars* s, void* stream) {
+    Cfa cfa;
+    if (!hn_ptrs(sigma_map, sigma_mode)) return DDNM_E_BADARG;
+    if (int e = mosaic_args(B, H, W, et_bstride, pattern_host, ph, pw, &cfa)) return e;
+    if (int e = hn_model(sigma_mode, s2, g, k.st, k.st2, k.c1, k.c2)) return e;
+    const int64_t hw4 = (int64_t)H * W / 4, total4 = B * hw4;
+    if (sigma_mode == DDNM_HN_MAP)
+        DDNM_LAUNCH((step_plus_mosaic_hn_kernel<Src, SigmaMap>), GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et,
+                    et_bstride, src, y, SigmaMap{sigma_map}, x0_out, xt_next, W, hw4, total4, *s, cfa, k);
+    else
+        DDNM_LAUNCH((step_plus_mosaic_hn_kernel<Src, SigmaShot>), GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et,
+                    et_bstride, src, y, SigmaShot{s2, g}, x0_out, xt_next, W, hw4, total4, *s, cfa, k);
+    return 0;
+}
+
+template <class Src>
+static int launch_step_plus_denoise_hn(const float* xt, const float* et, int64_t et_bstride, Src src, const float* y, float* x0_out,
+                                       float* xt_next, int32_t B, int64_t chw, const float* sigma_map, int32_t sigma_mode, float s2,
+                                       float g, HnCoef k, const ddnm_step_scalars* s, void* stream) {
+    if (!hn_ptrs(sigma_map, sigma_mode) || B <= 0 || chw <= 0) return DDNM_E_BADARG;
+    if ((chw & 3) || (et_bstride & 3)) return DDNM_E_SHAPE;
+    if (int e = hn_model(sigma_mode, s2, g, k.st, k.st2, k.c1, k.c2)) return e;
+    const int64_t total4 = (int64_t)B * chw / 4;
+    if (sigma_mode == DDNM_HN_MAP)
+        DDNM_LAUNCH((step_plus_denoise_hn_kernel<Src, SigmaMap>), GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et,
+                    et_bstride, src, y, SigmaMap{sigma_map}, x0_out, xt_next, chw / 4, total4, *s, k);
+    else
+        DDNM_LAUNCH((step_plus_denoise_hn_kernel<Src, SigmaShot>), GRID_1D(total4), dim3(256), 0, (hipStream_t)stream, xt, et,
+                    et_bstride, src, y, SigmaShot{s2, g}, x0_out, xt_next, chw / 4, total4, *s, k);
+    return 0;
+}
+
+extern "C" int ddnm_step_plus_mosaic_hn_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                            const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                            const uint8_t* pattern_host, int32_t ph, int32_t pw, const float* sigma_map,
+                                            int32_t sigma_mode, float s2, float g, float sigma_t, float sigma_t2, float c1,
+                                            float c2, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !x0_out || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_plus_mosaic_hn(xt, et, et_bstride, noise_src(noise, s, (int64_t)3 * H * W), y, x0_out, xt_next, B, H, W,
+                                      pattern_host, ph, pw, sigma_map, sigma_mode, s2, g, HnCoef{sigma_t, sigma_t2, c1, c2}, s,
+                                      stream);
+}
+
+extern "C" int ddnm_step_plus_mosaic_hn_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                                  const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H,
+                                                  int32_t W, const uint8_t* pattern_host, int32_t ph, int32_t pw,
+                                                  const float* sigma_map, int32_t sigma_mode, float s2, float g, float sigma_t,
+                                                  float sigma_t2, float c1, float c2, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !x0_out || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_plus_mosaic_hn(xt, et, et_bstride, keyed_src(keys, s, (int64_t)3 * H * W), y, x0_out, xt_next, B, H, W,
+                                      pattern_host, ph, pw, sigma_map, sigma_mode, s2, g, HnCoef{sigma_t, sigma_t2, c1, c2}, s,
+                                      stream);
+}
+
+extern "C" int ddnm_step_plus_denoise_hn_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise,
+                                             const float* y, float* x0_out, float* xt_next, int32_t B, int64_t chw,
+                                             const float* sigma_map, int32_t sigma_mode, float s2, float g, float sigma_t,
+                                             float sigma_t2, float c1, float c2, const ddnm_step_scalars* s, void* stream) {
+    if (!xt || !et || !y || !x0_out || !xt_next || !s || !noise_ok(noise, s)) return DDNM_E_BADARG;
+    return launch_step_plus_denoise_hn(xt, et, et_bstride, noise_src(noise, s, chw), y, x0_out, xt_next, B, chw, sigma_map,
+                                       sigma_mode, s2, g, HnCoef{sigma_t, sigma_t2, c1, c2}, s, stream);
+}
+
+extern "C" int ddnm_step_plus_denoise_hn_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* keys,
+                                                   const float* y, float* x0_out, float* xt_next, int32_t B, int64_t chw,
+                                                   const float* sigma_map, int32_t sigma_mode, float s2, float g, float sigma_t,
+                                                   float sigma_t2, float c1, float c2, const ddnm_step_scalars* s,
+                                                   void* stream) {
+    if (!xt || !et || !y || !x0_out || !xt_next || !s || !keys_ok(keys)) return DDNM_E_BADARG;
+    return launch_step_plus_denoise_hn(xt, et, et_bstride, keyed_src(keys, s, chw), y, x0_out, xt_next, B, chw, sigma_map,
+                                       sigma_mode, s2, g, HnCoef{sigma_t, sigma_t2, c1, c2}, s, stream);
+}
+
 // ---------------------------------------------------------------- keyed entry points: same launchers, per-image keys
 extern "C" int ddnm_step_combine_keyed_f32(const float* x0, const float* proj, const float* apy, const uint32_t* keys,
                                            const float* et, int64_t et_bstride, float* xt_next, int32_t B, int64_t chw,

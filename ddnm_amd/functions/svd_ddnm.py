@@ -59,7 +59,7 @@ import os
 import torch
 
 from .. import _lib, ops
-from .svd_operators import A_functions, _axpby
+from .svd_operators import HN_OPERATORS, A_functions, NoiseModel, _axpby
 
 class_num = 951      # svd_ddnm.py:7
 
@@ -400,14 +400,33 @@ def ddnm_plus_diffusion(x, model, b, eta, A_funcs, y, sigma_y, cls_fn=None, clas
     HIP kernel; per step: UNet forward, x0 kernel, A / A^+ kernels, Lambda, Lambda_noise, combine.  An operator with a
     non-None `ddnm_plus_step` hook (SRConv, Deblurring2D: no Lambda in the reference) runs the whole operator part of the
     step in its spectral planes instead: `begin_plus_run(y)` once, then x0 kernel, two two-sided GEMMs and one fused kernel
-    per step (svd_operators._SpectralPlus)."""
+    per step (svd_operators._SpectralPlus).  `sigma_y` is the noise level on the engine's [-1, 1] scale, or a
+    `svd_operators.NoiseModel`: its scalar form runs what the float runs, shot + read noise and noise maps run the
+    one-launch `ddnm_plus_step_hn` of Mosaic / Denoising (every other operator: ValueError)."""
     if not x.is_cuda:
         raise RuntimeError("ddnm_amd.ddnm_plus_diffusion runs on the GPU only (no CPU fallback)")
     plus_step = getattr(A_funcs, "ddnm_plus_step", None)     # SRConv / Deblurring2D: the step fused in the spectral planes
+    begin = A_funcs.begin_plus_run if plus_step is not None else None
+    # `sigma_y` as a NoiseModel: the scalar form IS the float (same launches); shot + read noise and noise maps run the
+    # operator's one-launch per-entry step (Mosaic, Denoising: U = I and singular value 1, where the model is exact)
+    hn_step = None
+    if isinstance(sigma_y, NoiseModel):
+        model_y = sigma_y
+        if model_y.is_scalar:
+            sigma_y = model_y.sigma_engine()
+        else:
+            hn_step = getattr(A_funcs, "ddnm_plus_step_hn", None)
+            if hn_step is None:
+                raise ValueError(f"per-entry measurement noise (a {model_y.kind} NoiseModel) is supported by {HN_OPERATORS}, "
+                                 f"not by {type(A_funcs).__name__}: pass a scalar sigma_y")
+            begin = lambda y: A_funcs.begin_plus_run(y, model_y)
 
     def step(it, xt, et, y, noise, x0_t, out):
         a, sigma_t = it.at_next.sqrt(), (1 - it.at_next).sqrt()
         s = ops.step_scalars(it.at, it.at_next, eta)
+        if hn_step is not None:
+            hn_step(xt, et, noise.kernel_arg(s, it.k), s, float(sigma_t), eta, x0_t, out)
+            return
         if plus_step is not None:
             plus_step(xt, et, noise.kernel_arg(s, it.k), s, sigma_y, float(sigma_t), eta, x0_t, out)
             return
@@ -421,5 +440,5 @@ def ddnm_plus_diffusion(x, model, b, eta, A_funcs, y, sigma_y, cls_fn=None, clas
 
     # begin_plus_run: y^ of THIS call's measurement; never cached across runs
     xt, x0_t = _reverse_loop(x, model, b, y, config, _noise_source(noise, x), step,
-                             begin=A_funcs.begin_plus_run if plus_step is not None else None, cls_fn=cls_fn, record=record)
+                             begin=begin, cls_fn=cls_fn, record=record)
     return _finish(xt, x0_t, return_cpu)

@@ -90,6 +90,170 @@ def cs_plus_coefficients(a, sigma_y, sigma_t, eta):
     return float(a) * lam, d1n, d2n, d1r - d1n, d2r - d2n
 
 
+HN_OPERATORS = "Mosaic (--deg demosaic_*) and Denoising (--deg denoising)"
+
+
+def noise_map_row(arr, n, image_shape=None, name="the noise map"):
+    """A per-entry noise map -> its validated float32 row [n] (the [0, 1] scale it was stated on).  `arr` holds one
+    standard deviation per measurement entry, as [n], [1, n] or the operator's `measurement_image_shape()`; the entries
+    are finite and non-negative (zeros are allowed: an entry measured exactly).  `name` is the file the errors speak of."""
+    a = np.asarray(arr)
+    if a.dtype.kind not in "fiu":
+        raise ValueError(f"{name}: a noise map is a float array of {n} standard deviations, got dtype {a.dtype}")
+    shapes = [(n,), (1, n)] + ([tuple(image_shape)] if image_shape is not None else [])
+    if tuple(a.shape) not in shapes:
+        raise ValueError(f"{name}: a noise map holds one row of {n} entries, shaped "
+                         f"{' or '.join(str(list(s)) for s in shapes)} (one row for every image of the run); got shape "
+                         f"{list(a.shape)} with {a.size} entries")
+    row = np.ascontiguousarray(a.reshape(-1), dtype=np.float32)
+    if not np.isfinite(row).all():
+        bad = int((~np.isfinite(row)).sum())
+        raise ValueError(f"{name}: the {n} entries of a noise map are finite, got {bad} that are inf or nan "
+                         f"(the first at entry {int(np.flatnonzero(~np.isfinite(row))[0])})")
+    if (row < 0).any():
+        raise ValueError(f"{name}: the {n} entries of a noise map are standard deviations >= 0, got {int((row < 0).sum())} "
+                         f"negative ones (minimum {float(row.min())!r})")
+    return row
+
+
+class NoiseModel:
+    """The noise of a measurement, where `ddnm_plus_diffusion` takes the scalar `sigma_y`; every figure is stated on the
+    [0, 1] scale of `--sigma_y` (the engine works on [-1, 1] and doubles it).  Three forms:
+
+      NoiseModel.scalar(s)        every entry has the standard deviation s: exactly `--sigma_y s`, today's launches
+      NoiseModel.shot(s, g)       shot + read noise: Var_j = s^2 + g u_j with u_j = clamp((y_j + 1) / 2, 0, 1) the measured
+                                  intensity (the plug-in estimate), so sigma_j = 2 sqrt(s^2 + g u_j) on the engine's scale;
+                                  g = 0 is the scalar form
+      NoiseModel.map(row)         one standard deviation per measurement entry (`noise_map_row`), shared by every image
+
+    The per-entry forms are exact for operators whose U is the identity and whose measured entries have singular value 1
+    -- a diagonal covariance is diagonal in their spectral basis --, which here are Mosaic and Denoising (`ddnm_plus_step_hn`)."""
+
+    def __init__(self, kind, sigma=0.0, gain=0.0, row=None):
+        self.kind, self.sigma, self.gain, self.row = kind, float(sigma), float(gain), row
+        self._dev = {}
+
+    @classmethod
+    def scalar(cls, sigma):
+        sigma = float(sigma)
+        if not np.isfinite(sigma) or sigma < 0:
+            raise ValueError(f"sigma_y is a finite standard deviation >= 0, got {sigma!r}")
+        return cls("scalar", sigma)
+
+    @classmethod
+    def shot(cls, sigma, gain):
+        sigma, gain = float(sigma), float(gain)
+        if not np.isfinite(gain) or gain < 0:
+            raise ValueError(f"sigma_y_shot is a finite shot-noise gain >= 0 (Var = sigma_y^2 + gain * intensity), got {gain!r}")
+        base = cls.scalar(sigma)
+        return base if gain == 0 else cls("shot", sigma, gain)
+
+    @classmethod
+    def map(cls, row, n=None, image_shape=None, name="the noise map"):
+        row = noise_map_row(row, np.asarray(row).size if n is None else n, image_shape, name)
+        return cls("map", row=row)
+
+    @classmethod
+    def from_options(cls, sigma_y, sigma_y_shot=0.0, sigma_y_map=None, op=None):
+        """The model of the command line: `--sigma_y s [--sigma_y_shot g]` or `--sigma_y_map FILE.npy` (with --sigma_y 0
+        or unset, and no --sigma_y_shot); `op` is the operator whose measurement the map describes."""
+        if sigma_y_map is None:
+            return cls.shot(sigma_y, sigma_y_shot or 0.0)
+        if float(sigma_y or 0.0) != 0.0 or float(sigma_y_shot or 0.0) != 0.0:
+            raise ValueError(f"--sigma_y_map {sigma_y_map} states the noise of every entry: --sigma_y and --sigma_y_shot must "
+                             f"be 0 or unset with it, got --sigma_y {sigma_y} --sigma_y_shot {sigma_y_shot or 0.0}")
+        if op is None or not hasattr(op, "ddnm_plus_step_hn"):
+            raise ValueError(f"--sigma_y_map: per-entry measurement noise is supported by {HN_OPERATORS}, not by "
+                             f"{type(op).__name__}")
+        try:
+            arr = np.load(sigma_y_map, allow_pickle=False)
+        except (OSError, ValueError) as e:
+            raise ValueError(f"--sigma_y_map {sigma_y_map}: not a readable .npy array ({e})") from None
+        return cls.map(arr, op.measurement_size(), op.measurement_image_shape(), str(sigma_y_map))
+
+    @property
+    def is_scalar(self):
+        return self.kind == "scalar"
+
+    def sigma_engine(self):
+        """The scalar form's sigma_y on the engine's [-1, 1] scale: what `ddnm_plus_diffusion` takes as a float."""
+        if not self.is_scalar:
+            raise ValueError(f"a {self.kind} noise model has no single sigma_y")
+        return 2 * self.sigma
+
+    def device_row(self, device):
+        """The map's row on the engine's scale (2 x, exact in fp32) on `device`; one copy per device."""
+        key = str(torch.device(device))
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.row * np.float32(2)).to(device).contiguous()
+        return t
+
+    def std(self, y_clean):
+        """sigma_j on the engine's scale for the clean measurement rows `y_clean` [b, n] (the simulation of --add_noise:
+        shot noise takes the clean intensity): a tensor that broadcasts against [b, n]."""
+        if self.kind == "scalar":
+            return torch.full((1, 1), 2 * self.sigma, dtype=torch.float32, device=y_clean.device)
+        if self.kind == "map":
+            if y_clean.shape[-1] != self.row.size:
+                raise ValueError(f"the noise map has {self.row.size} entries, the measurement rows have {y_clean.shape[-1]}")
+            return self.device_row(y_clean.device).reshape(1, -1)
+        u = ((y_clean.float() + 1) * 0.5).clamp(0, 1)
+        return 2 * (self.sigma ** 2 + self.gain * u).sqrt()
+
+    def settings(self):
+        """What a saved measurement records of the model next to `sigma_y`: the shot gain, and a map's SHA-256 (of its
+        float32 little-endian row on the [0, 1] scale) and length."""
+        import hashlib
+        out = {"sigma_y_shot": self.gain, "sigma_y_map_sha256": None, "sigma_y_map_len": None}
+        if self.kind == "map":
+            out["sigma_y_map_sha256"] = hashlib.sha256(self.row.astype("<f4").tobytes()).hexdigest()
+            out["sigma_y_map_len"] = int(self.row.size)
+        return out
+
+    def kernel_args(self, device, n):
+        """(sigma_map, sigma_mode, s2, g) of the `*_hn_*` entry points (include/ddnm_hip.h) for rows of n entries."""
+        if self.kind == "map":
+            if self.row.size != n:
+                raise ValueError(f"the noise map has {self.row.size} entries, the operator's measurement has {n}")
+            return _p(self.device_row(device)), 0, 0.0, 0.0
+        if self.kind == "shot":
+            return None, 1, self.sigma ** 2, self.gain
+        raise ValueError("the scalar noise model runs the scalar DDNM+ step (pass sigma_engine())")
+
+
+class _PerEntryNoisePlus:
+    """DDNM+ with a per-entry `NoiseModel` (shot + read, or a map) in ONE launch: the hook `ddnm_plus_diffusion` calls
+    when it is handed a non-scalar model.  `begin_plus_run(y, noise_model)` keeps y -- and moves the map's row to the
+    device -- for the run; the class names its entry point and geometry in `_hn_launch`."""
+
+    def begin_plus_run(self, y, noise_model=None):
+        y = _flat(y)
+        B, n = y.shape[0], self.measurement_size()
+        if y.shape[1] != n:
+            raise ValueError(f"y must be [{B}, {n}], got {tuple(y.shape)}")
+        self._plus_run = (B, ops._f32c(y, "y"))
+        self._plus_hn = None
+        if noise_model is not None:
+            self._plus_hn = noise_model.kernel_args(y.device, n) + (noise_model,)      # (the model keeps the row alive)
+
+    def ddnm_plus_step_hn(self, xt, et, noise, s, sigma_t, eta, x0_out, xt_next):
+        """One DDNM+ reverse step under the run's per-entry noise model in one launch: x0|t into `x0_out` (uncorrected),
+        x_{t-1} into `xt_next`; `et` may be the [:, :3] view of a 6-channel network output."""
+        B = xt.shape[0]
+        y, = _plus_state(self, B)
+        if getattr(self, "_plus_hn", None) is None:
+            raise RuntimeError("ddnm_plus_step_hn needs begin_plus_run(y, noise_model) for this batch first")
+        n_x = B * self.channels * self.img_dim ** 2
+        for name, t in (("xt", xt), ("x0_out", x0_out), ("xt_next", xt_next)):
+            if ops._f32c(t, name).numel() != n_x:
+                raise ValueError(f"ddnm_plus_step_hn: {name} has {t.numel()} entries, expected {n_x}")
+        sigma_t, eta = float(sigma_t), float(eta)
+        fn, geometry = self._hn_launch(B)
+        ops.step_call(fn, xt, et, noise, y, _p(x0_out), _p(xt_next), *geometry, *self._plus_hn[:4], sigma_t, sigma_t ** 2,
+                      sigma_t * eta, sigma_t * (1 - eta ** 2) ** 0.5, s)
+
+
 def _flat(vec):
     v = vec.reshape(vec.shape[0], -1)
     if v.dtype != torch.float32 or not v.is_contiguous():
@@ -287,7 +451,7 @@ class A_functions:
         ops.step_combine(x0_out, proj, None, noise, et, s, out=xt_next)
 
 
-class Denoising(A_functions):
+class Denoising(_PerEntryNoisePlus, A_functions):
     def __init__(self, channels, img_dim, device):
         self.channels, self.img_dim, self.device = channels, img_dim, device
 
@@ -324,6 +488,11 @@ class Denoising(A_functions):
     def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
         B = xt.shape[0]
         ops.step_call("ddnm_step_denoise_f32", xt, et, noise, y, _p(x0_out), _p(xt_next), B, xt.numel() // B, s)
+
+    # A per-entry NoiseModel runs the DDNM+ step in ONE launch (`begin_plus_run(y, noise_model)`, `ddnm_plus_step_hn` of
+    # _PerEntryNoisePlus); the scalar sigma_y keeps the reference's Lambda / Lambda_noise chain above (no `ddnm_plus_step`).
+    def _hn_launch(self, B):
+        return "ddnm_step_plus_denoise_hn_f32", (B, self.channels * self.img_dim ** 2)
 
 
 class _RowOperator(A_functions):
@@ -740,7 +909,7 @@ def cfa_pattern(pattern):
     return np.ascontiguousarray(p, dtype=np.uint8)
 
 
-class Mosaic(_MissingEntries):
+class Mosaic(_PerEntryNoisePlus, _MissingEntries):
     """Demosaicing: a raw sensor frame keeps ONE colour sample per pixel, behind the periodic colour filter array
     `pattern` (a name of CFA_PATTERNS or a [ph, pw] array of channel codes).  It is the reference's Inpainting
     (svd_operators.py:324-439) over the HWC-interleaved entries with the two channels a pixel does not sample missing:
@@ -806,9 +975,9 @@ class Mosaic(_MissingEntries):
 
     # ---- DDNM+ (sigma_y > 0): the engine hook of `ddnm_plus_diffusion`.  Lambda / Lambda_noise above stay callable (the
     # reference's object protocol); the loop takes the one fused launch instead of their eight.
-    def begin_plus_run(self, y):
-        y = _flat(y)
-        self._plus_run = (y.shape[0], self._check_y(y, y.shape[0]))
+    # `begin_plus_run(y, noise_model=None)` and `ddnm_plus_step_hn` (a per-entry NoiseModel) come from _PerEntryNoisePlus.
+    def _hn_launch(self, B):
+        return "ddnm_step_plus_mosaic_hn_f32", (B, self.img_dim, self.img_dim, *self._cfa)
 
     def ddnm_plus_step(self, xt, et, noise, s, sigma_y, sigma_t, eta, x0_out, xt_next):
         """One DDNM+ reverse step in one launch: x0|t into `x0_out` (uncorrected, as the loop returns and time-travels

@@ -69,8 +69,8 @@ from .. import dist as ddist
 from .. import ops
 from ..functions.svd_ddnm import (_AtenNoise, _reverse_loop, _TapeNoise, ddnm_diffusion, ddnm_plus_diffusion,
                                   get_schedule_jump)
-from ..functions.svd_operators import (DEMOSAIC, Colorization, Denoising, Inpainting, InpaintingBank, SuperResolution,
-                                      build_operator, mask_color_sr, missing_indices_of_mask)
+from ..functions.svd_operators import (DEMOSAIC, HN_OPERATORS, Colorization, Denoising, Inpainting, InpaintingBank,
+                                      NoiseModel, SuperResolution, build_operator, mask_color_sr, missing_indices_of_mask)
 from .models import Model
 
 
@@ -197,6 +197,8 @@ MEASUREMENTS = "measurements:"                      # --path_y measurements:DIR:
 MEASUREMENT_EXT = (".npy", ".png", ".jpg", ".jpeg")
 MEASUREMENT_SETTINGS = "measurements.json"          # what DDNM_SAVE_Y=1 writes next to the y_{i}.npy: settings only
 MEASUREMENT_PINNED = ("deg", "deg_scale", "image_size", "channels")      # a folder's settings a run must agree with
+# ... and, where the folder records them (a run under --sigma_y_shot / --sigma_y_map), the per-entry noise model
+MEASUREMENT_NOISE_KEYS = ("sigma_y_shot", "sigma_y_map_sha256", "sigma_y_map_len")
 
 
 def measurement_dir(path_y, exp):
@@ -218,11 +220,33 @@ def save_y():
     return v == "1"
 
 
-def run_settings(args, config, sigma_y):
-    """The settings a saved measurement depends on (`sigma_y` on the command line's [0, 1] scale)."""
-    return {"deg": args.deg, "deg_scale": float(args.deg_scale), "image_size": int(config.data.image_size),
-            "channels": int(config.data.channels), "sigma_y": float(sigma_y), "add_noise": bool(args.add_noise),
-            "seed": int(args.seed)}
+def run_settings(args, config, sigma_y, noise_model=None):
+    """The settings a saved measurement depends on (`sigma_y` on the command line's [0, 1] scale); a per-entry
+    `noise_model` (shot + read noise, a noise map) adds its shot gain and the map's SHA-256 and length."""
+    out = {"deg": args.deg, "deg_scale": float(args.deg_scale), "image_size": int(config.data.image_size),
+           "channels": int(config.data.channels), "sigma_y": float(sigma_y), "add_noise": bool(args.add_noise),
+           "seed": int(args.seed)}
+    if noise_model is not None and not noise_model.is_scalar:
+        out.update(noise_model.settings())
+    return out
+
+
+def noise_model_of(args, op=None):
+    """The NoiseModel of the command line (--sigma_y, --sigma_y_shot, --sigma_y_map; [0, 1] scale) for operator `op`:
+    the scalar form unless one of the two new flags is given; a per-entry form needs an operator with the hook."""
+    shot, path = float(getattr(args, "sigma_y_shot", 0.0) or 0.0), getattr(args, "sigma_y_map", None)
+    nm = NoiseModel.from_options(args.sigma_y, shot, path, op)
+    if not nm.is_scalar and not hasattr(op, "ddnm_plus_step_hn"):
+        raise ValueError(f"--sigma_y_shot / --sigma_y_map: per-entry measurement noise is supported by {HN_OPERATORS}, "
+                         f"not by --deg {args.deg} ({type(op).__name__})")
+    return nm
+
+
+def check_noise_flags(args, simplified):
+    """--sigma_y_shot / --sigma_y_map belong to the SVD path's DDNM+ loop."""
+    if simplified and (float(getattr(args, "sigma_y_shot", 0.0) or 0.0) != 0.0 or getattr(args, "sigma_y_map", None)):
+        raise ValueError("--simplified with --sigma_y_shot / --sigma_y_map: the simplified loop knows one sigma_y; "
+                         "per-entry measurement noise runs on the SVD path only")
 
 
 def check_measurements(args, simplified):
@@ -295,6 +319,15 @@ class MeasurementFolder(data.Dataset):
             if key in have and have[key] != run[key]:
                 raise ValueError(f"{os.path.join(self.root, MEASUREMENT_SETTINGS)}: the measurements were formed with "
                                  f"{key} = {have[key]!r}, this run has {key} = {run[key]!r}")
+
+    def check_noise_settings(self, run):
+        """The per-entry noise model the folder records (MEASUREMENT_NOISE_KEYS of its measurements.json) against this
+        run's: another shot gain, another map or none is refused; a folder that records none leaves the run free."""
+        have = self.settings() or {}
+        for key in MEASUREMENT_NOISE_KEYS:
+            if key in have and have[key] != run.get(key, 0.0 if key == "sigma_y_shot" else None):
+                raise ValueError(f"{os.path.join(self.root, MEASUREMENT_SETTINGS)}: the measurements were formed with "
+                                 f"{key} = {have[key]!r}, this run has {key} = {run.get(key)!r}")
 
     def __len__(self):
         return len(self.names)
@@ -765,6 +798,7 @@ class Diffusion(object):
     def sample(self, simplified):
         check_samples(samples(), simplified)
         check_measurements(self.args, simplified)
+        check_noise_flags(self.args, simplified)
         save_y()
         model = self._build_model()
         # batch sizes of 1 and 2 (the reference's shipped `sampling.batch_size: 1`) replay the forward from a hipGraph:
@@ -885,9 +919,14 @@ class Diffusion(object):
         measured = isinstance(loader.dataset, MeasurementFolder)
         if measured:
             loader.dataset.bind(A_funcs, config, args.subset_start)
-        settings = run_settings(args, config, args.sigma_y)
+        # --sigma_y_shot / --sigma_y_map: a per-entry NoiseModel in sigma_y's place (scalar: the float, as before)
+        noise_model = noise_model_of(args, A_funcs)
+        settings = run_settings(args, config, args.sigma_y, noise_model)
+        if measured:
+            loader.dataset.check_noise_settings(settings)
         args.sigma_y = 2 * args.sigma_y          # scaling to [-1, 1] (:524)
         sigma_y = args.sigma_y
+        per_entry = not noise_model.is_scalar
         rank, world = ddist.world_state()      # the INITIALISED group (env-only sharding without a group loses shards)
         print(f"Start from {args.subset_start}")
         C, S, batch_size = config.data.channels, config.data.image_size, config.sampling.batch_size
@@ -961,10 +1000,12 @@ class Diffusion(object):
             A_batch = A_funcs if bank is None else bank.for_images(range(idx0, idx0 + b))
             y = given(batch, A_batch) if measured else A_batch.A(x_orig)
             if args.add_noise:
+                # a per-entry model simulates itself: sigma_j of the CLEAN y (shot noise: the clean intensity), same draw
+                std = noise_model.std(y.reshape(b, -1)).expand(b, -1).reshape(y.shape) if per_entry else sigma_y
                 if philox:
-                    y = y + measurement_noise(_mix64(args.seed, bi) ^ 0x5DEECE66D, y.reshape(b, -1)).reshape(y.shape) * sigma_y
+                    y = y + measurement_noise(_mix64(args.seed, bi) ^ 0x5DEECE66D, y.reshape(b, -1)).reshape(y.shape) * std
                 else:
-                    y = y + noise[0].draw(tuple(y.shape)) * sigma_y
+                    y = y + noise[0].draw(tuple(y.shape)) * std
                     for tape in noise[1:]:
                         tape.draw(tuple(y.shape))    # the samples share y; each tape still moves as in its own run
             if writer:
@@ -998,7 +1039,10 @@ class Diffusion(object):
             x, y = _cat([p.x_T for p in parts]), _cat(ys)
             # noise-free: DDNM (diffusion.py:587-588); noisy: DDNM+, which takes sigma_y after y (:589-590).  classes=None:
             # the samplers take the class from the config, like the reference
-            sampler, extra = (ddnm_diffusion, ()) if sigma_y == 0.0 else (ddnm_plus_diffusion, (sigma_y,))
+            if per_entry:
+                sampler, extra = ddnm_plus_diffusion, (noise_model,)
+            else:
+                sampler, extra = (ddnm_diffusion, ()) if sigma_y == 0.0 else (ddnm_plus_diffusion, (sigma_y,))
             with torch.no_grad():
                 xs, _ = sampler(x, model, self.betas, args.eta, op, y, *extra, cls_fn=cls_fn, classes=None, config=config,
                                 noise=noise, return_cpu=False)

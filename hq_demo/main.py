@@ -111,7 +111,15 @@ def parse(argv=None):
     parser.add_argument("--resize_y", default=False, action="store_true")
     parser.add_argument("--path_y", type=str, required=False, default="data/datasets/gts/inet256/orange.png")
     parser.add_argument("--class", type=int, required=False, default=950)
-    return vars(parser.parse_args(argv))
+    # the per-entry noise model of the SVD path's runner: named here so that the refusal says why
+    parser.add_argument("--sigma_y_shot", type=float, required=False, default=0.)
+    parser.add_argument("--sigma_y_map", type=str, required=False, default=None)
+    cli = vars(parser.parse_args(argv))
+    shot, noise_map = cli.pop("sigma_y_shot"), cli.pop("sigma_y_map")
+    if shot != 0. or noise_map is not None:
+        parser.error("--sigma_y_shot / --sigma_y_map: hq_demo knows one --sigma_y; per-entry measurement noise is restored "
+                     "by the SVD path (main.py --deg demosaic_* | denoising)")
+    return cli
 
 
 if __name__ == "__main__":

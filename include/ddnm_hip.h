@@ -32,7 +32,7 @@ int ddnm_version(void);                 /* ABI version, currently 7 (bumped on e
                                            per-image inpainting entry points *_pi_* were added under 7: new symbols
                                            only, no struct and no existing prototype changed; the demosaicing entry
                                            points *_mosaic_*, the old-photo ones *_mcsr_* and the chroma ones
-                                           *_chroma_* likewise) */
+                                           *_chroma_* and the per-entry-noise ones *_hn_* likewise) */
 const char* ddnm_build_digest(void);    /* sha256 of the sources + flags this binary was built from (build.py) */
 int ddnm_sizeof(int which);             /* sizeof of 0: ddnm_conv_desc, 1: ddnm_gemm_desc, 2: ddnm_conv16_desc,
                                            3: ddnm_step_scalars as compiled into the binary (-1: unknown index) */
@@ -730,6 +730,51 @@ int ddnm_step_plus_mosaic_keyed_f32(const float* xt, const float* et, int64_t et
                                     const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
                                     const uint8_t* pattern_host, int32_t ph, int32_t pw, float a_lambda, float d1n,
                                     float d2n, float dd1, float dd2, const ddnm_step_scalars* s, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * DDNM+ with per-entry measurement noise ("hn": heteroscedastic noise) for the mosaic and for denoising.  Added under
+ * ABI 7: new symbols only; ddnm_step_scalars keeps its size, the noise model travels in the arguments.
+ * Both operators have U = I and singular value 1 on every measured entry (functions/svd_operators.py:324-439 over
+ * single entries, :442-476), so a diagonal noise covariance diag(sigma_j^2) is diagonal in their spectral basis and the
+ * per-singular-value rules the reference spells out with change_index masks (svd_operators.py:367-436; the step is
+ * functions/svd_ddnm.py:118-131) hold per entry j with sigma_y -> sigma_j.  With a = s->sqrt_at_next, thr = a sigma_j:
+ *   sigma_j == 0 or a == 0 : (a lambda, d1, d2) = (a, c1, c2)
+ *   sigma_t < thr          : (a * (c2 / thr), c1, 0)
+ *   sigma_t > thr          : (a, sqrt(max(sigma_t2 - thr * thr, 0)), 0)
+ *   sigma_t == thr         : (a, c1, c2)
+ *   x0      = (xt - et * sqrt_1m_at) / sqrt_at                        -> x0_out, uncorrected (required)
+ *   x_{t-1} = ((a x0 - a lambda (x0 - y)) + d1 n) + d2 et             measured entries
+ *   x_{t-1} = ((a x0 - 0 (x0 - y)) + c1 n) + c2 et                    the two planes a mosaic pixel does not sample
+ * in fp32, one rounding per operation, in that order.  sigma_t, sigma_t2 = sigma_t^2, c1 = sigma_t eta and
+ * c2 = sigma_t sqrt(1 - eta^2) come from the host (evaluated in double); s->c1, s->c2 and s->lambda are not read.
+ *   sigma_mode 0 (map):  sigma_j = sigma_map[j], a DEVICE row on the engine's [-1, 1] scale (twice the [0, 1] value),
+ *                        16-byte aligned, H*W (mosaic) or chw (denoising) entries, shared by every image of the batch;
+ *                        s2 and g are ignored.
+ *   sigma_mode 1 (shot): sigma_j = 2 sqrt(s2 + g u_j), u_j = clamp((y_j + 1) / 2, 0, 1): read variance s2 and shot gain g
+ *                        on the [0, 1] scale, the intensity taken from the measurement itself; sigma_map is ignored.
+ * Noise sources, et and the mosaic's pattern_host as for ddnm_step_plus_mosaic_f32.  NULL pointer (the row in map mode
+ * included, or a misaligned one), non-positive size, no noise source: DDNM_E_BADARG; then H % 4, W % 4, chw % 4 or
+ * et_bstride % 4 != 0, a bad pattern, a sigma_mode other than 0 / 1, a negative or non-finite s2, g (shot mode),
+ * sigma_t or sigma_t2, a non-finite c1 or c2: DDNM_E_SHAPE.  All of it is checked before any launch.
+ * ------------------------------------------------------------------------- */
+int ddnm_step_plus_mosaic_hn_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                                 float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                 const uint8_t* pattern_host, int32_t ph, int32_t pw, const float* sigma_map,
+                                 int32_t sigma_mode, float s2, float g, float sigma_t, float sigma_t2, float c1, float c2,
+                                 const ddnm_step_scalars* s, void* stream);
+int ddnm_step_plus_mosaic_hn_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                       const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W,
+                                       const uint8_t* pattern_host, int32_t ph, int32_t pw, const float* sigma_map,
+                                       int32_t sigma_mode, float s2, float g, float sigma_t, float sigma_t2, float c1,
+                                       float c2, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_plus_denoise_hn_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y,
+                                  float* x0_out, float* xt_next, int32_t B, int64_t chw, const float* sigma_map,
+                                  int32_t sigma_mode, float s2, float g, float sigma_t, float sigma_t2, float c1, float c2,
+                                  const ddnm_step_scalars* s, void* stream);
+int ddnm_step_plus_denoise_hn_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys,
+                                        const float* y, float* x0_out, float* xt_next, int32_t B, int64_t chw,
+                                        const float* sigma_map, int32_t sigma_mode, float s2, float g, float sigma_t,
+                                        float sigma_t2, float c1, float c2, const ddnm_step_scalars* s, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Old-photo restoration: mask, then grey, then r x r average pool in ONE operator -- the A of the simplified path's

@@ -52,6 +52,11 @@ FLAGS = [
     (("-n", "--noise_type"), dict(type=str, default="gaussian", help="accepted for compatibility (unused, like in the reference)")),
     (("--add_noise",), dict(action="store_true")),
 ]
+# flags the reference parser does not have: the measurement-noise model of DDNM+ beyond one sigma_y
+ENGINE_FLAGS = [
+    (("--sigma_y_shot",), dict(type=float, default=0.0, help="shot-noise gain g >= 0 on the [0,1] scale: Var = sigma_y^2 + g * intensity per measured entry (--deg demosaic_* and denoising)")),
+    (("--sigma_y_map",), dict(type=str, default=None, help="FILE.npy with the std of every measurement entry on the [0,1] scale, one row shared by all images (--deg demosaic_* and denoising; --sigma_y must be 0 or unset)")),
+]
 
 
 def to_namespace(tree):
@@ -63,7 +68,7 @@ def to_namespace(tree):
 
 def parse_args_and_config(argv=None):
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    for names, kw in FLAGS:
+    for names, kw in FLAGS + ENGINE_FLAGS:
         parser.add_argument(*names, **kw)
     args = parser.parse_args(argv)
 
@@ -133,7 +138,7 @@ def maybe_self_launch(argv):
     if n <= 1:
         return
     parser = argparse.ArgumentParser(add_help=False)
-    for names, kw in FLAGS:
+    for names, kw in FLAGS + ENGINE_FLAGS:
         parser.add_argument(*names, **kw)
     pre, _ = parser.parse_known_args(sys.argv[1:] if argv is None else argv)
     pre.image_folder = os.path.join(pre.exp, "image_samples", pre.image_folder)
