@@ -296,6 +296,20 @@ PROTOTYPES = {
     "ddnm_step_plus_chroma_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_float,
                                                   c_float, c_float, POINTER(StepScalars), c_void_p]),
+    # JPEG (block DCT of the chroma planes, quantisation cells): colour matrix and the 128 steps are HOST arrays
+    "ddnm_jpeg_quality_tables": (c_int32, [c_int32, c_int32, POINTER(c_float), POINTER(c_float)]),
+    "ddnm_op_jpeg_T_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                     c_void_p]),
+    "ddnm_op_jpeg_A_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                     POINTER(c_float), c_float, c_void_p]),
+    "ddnm_op_jpeg_pinv_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float),
+                                        c_void_p]),
+    "ddnm_step_jpeg_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                     c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_float,
+                                     POINTER(StepScalars), c_void_p]),
+    "ddnm_step_jpeg_keyed_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_float,
+                                           POINTER(StepScalars), c_void_p]),
     "ddnm_renoise_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
     "ddnm_op_avgpool_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "ddnm_op_upsample_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),

@@ -21,7 +21,9 @@ as one (or a few) hand-written HIP kernels:
   ChromaSubsample  -> Y'CbCr 4:2:0 / 4:2:2 / 4:1:1: full-resolution luma, chroma averaged per rw x rh site, with the exact
                       A^+ = w+ (Y - Ybar) + M^-1 (Ybar, Cb, Cr); four singular values per launch (|w_Y| and the 3 x 3 SVD of
                       the site means), evaluated on the host; `ddnm_plus_step` is ONE kernel
-  WalshHadamardCS  -> separable FWHT (shuffle + LDS) + permuted mask (svd_operators.py:211-251)
+  JPEG             -> a baseline JPEG file: the 8 x 8 block-DCT coefficients of those planes (4:4:4 / 4:2:2 / 4:2:0), each
+                      known up to its quantisation cell; `ddnm_step` projects T x0 into the cell in ONE kernel; noise-free only
+  WalshHadamardCS -> separable FWHT (shuffle + LDS) + permuted mask (svd_operators.py:211-251)
   Denoising        -> identity                                   (svd_operators.py:442-462)
 
 Every class also implements `ddnm_step(...)`, the fused x0 / projection / DDIM
@@ -44,7 +46,7 @@ import ctypes
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from ..ops import _p
 
 
@@ -1427,6 +1429,147 @@ class ChromaSubsample(A_functions):
                       float(sigma_y), float(sigma_t), float(eta), s)
 
 
+JPEG_SITES = ((1, 1), (2, 1), (2, 2))                                                           # (rw, rh): 4:4:4, 4:2:2, 4:2:0
+JPEG_NAMES = {"jpeg_444": (1, 1), "jpeg_422": (2, 1), "jpeg_420": (2, 2)}
+JPEG_DC_SHIFT = -4.0 / 127.5            # an encoder subtracts 128 from 8-bit samples: the luma DC offset on the [-1, 1] scale
+
+
+def jpeg_quality_tables(quality, dc_shift=True):
+    """(q [128] float32 in x units, delta) of libjpeg's tables for `quality` 1..100 (`ddnm_jpeg_quality_tables`, host only):
+    luma [64] then chroma [64] in natural order, the 8-bit entry / 127.5."""
+    q, delta = (ctypes.c_float * 128)(), ctypes.c_float()
+    if int(quality) != quality or not 1 <= int(quality) <= 100:
+        raise ValueError(f"a JPEG quality is an integer in 1..100, got {quality!r}")
+    _lib.check(_lib.lib().ddnm_jpeg_quality_tables(int(quality), int(bool(dc_shift)), q, ctypes.byref(delta)),
+              "ddnm_jpeg_quality_tables")
+    return np.array(q[:], dtype=np.float32), float(delta.value)
+
+
+class JPEG(A_functions):
+    """A baseline JPEG file as a measurement: the 8 x 8 block-DCT coefficients of the planes of `ChromaSubsample`
+    (site (rw, rh) = (1,1) 4:4:4, (2,1) 4:2:2, (2,2) 4:2:0), each rounded to a multiple of its quantisation step.
+
+    `A_linear` = T: the planes Y | Cb | Cr, then per plane and 8 x 8 block the orthonormal DCT-II; coefficient (u, v) of
+    block (I, J) sits at plane position (8 I + u, 8 J + v), so a row has d^2 (1 + 2 / (rw rh)) entries like the chroma
+    operator's.  T has full row rank and `A_pinv` = T^+ = A_chroma^+ . IDCT is its exact pseudo-inverse.  `A` is the
+    encoder, y = q rint((T x - delta) / q) + delta (the dequantised cell centre; `levels(y)` are the integers), with the
+    steps q of libjpeg's tables for `quality` 1..100 -- or of `qtables`, a [2, 8, 8] integer array (luma, chroma; natural
+    order) that overrides it -- in x units (entry / 127.5), and delta = -4 / 127.5 on the luma DC only (`dc_shift`).
+    `A_pinv(y)` is what a JPEG decoder shows before clipping.
+
+    The measurement says which CELL a coefficient lay in, so `ddnm_step` pulls T x0 back into the cell, not onto its
+    centre:  x0h = x0 - lambda T^+(c - clamp(c, y - h, y + h)),  c = T x0,  h = box q / 2  (one launch, csrc/jpeg.hip).
+    `box` = 0 is the plain DDNM step against the centres; with `box` = 0.98 the restoration re-encodes to the measured
+    levels (clamped coefficients land on the cell edge; the 2 % margin keeps fp32 rounding out of the re-quantisation).
+    Quantisation error is bounded, not Gaussian: there is no `ddnm_plus_step`, and `Lambda` and friends stay
+    NotImplementedError.  `singulars()` is the chroma spectrum, which the orthogonal DCT does not change."""
+
+    def __init__(self, channels, img_dim, quality, rw, rh, device, matrix=None, qtables=None, dc_shift=True, box=0.98):
+        if channels != 3:
+            raise ValueError(f"JPEG splits RGB images into luma and chroma: channels must be 3, got {channels}")
+        if (rw, rh) not in JPEG_SITES:
+            raise ValueError(f"JPEG kernels have the sites (rw, rh) {', '.join(str(v) for v in JPEG_SITES)}: got {(rw, rh)!r}")
+        if img_dim % (8 * rw) or img_dim % (8 * rh):
+            raise ValueError(f"img_dim must be a multiple of the MCU ({8 * rw} x {8 * rh} pixels), got {img_dim}")
+        if not 0.0 <= float(box) <= 1.0:
+            raise ValueError(f"box is the share of the quantisation cell the step projects onto, in [0, 1]: got {box!r}")
+        self._chroma = ChromaSubsample(channels, img_dim, 2, 2, "cpu", matrix)     # the matrix checks; the site is set below
+        self.channels, self.img_dim, self.rw, self.rh, self.device = channels, img_dim, int(rw), int(rh), device
+        self.matrix, self._m = self._chroma.matrix, self._chroma._m
+        self.box, self.dc_shift = float(box), bool(dc_shift)
+        if qtables is None:
+            q, self.delta = jpeg_quality_tables(quality, dc_shift)
+            self.quality = int(quality)
+        else:
+            t = np.asarray(qtables)
+            if t.shape != (2, 8, 8) or not np.issubdtype(t.dtype, np.integer) or t.min() < 1 or t.max() > 65535:
+                raise ValueError("qtables is a [2, 8, 8] integer array (luma, chroma) of quantisation steps >= 1, got "
+                                 f"shape {t.shape}, dtype {t.dtype}")
+            q = (t.reshape(128).astype(np.float64) / 127.5).astype(np.float32)
+            self.delta = float(np.float32(JPEG_DC_SHIFT)) if dc_shift else 0.0
+            self.quality = None
+        self.q = q
+        self._q = (ctypes.c_float * 128)(*[float(v) for v in q])
+        d, n = img_dim, self.rw * self.rh
+        # q and delta of every entry of a measurement row (for `levels`): the block tables tiled over the planes
+        luma = np.tile(q[:64].reshape(8, 8), (d // 8, d // 8)).reshape(-1)
+        chroma = np.tile(q[64:].reshape(8, 8), (d // self.rh // 8, d // self.rw // 8)).reshape(-1)
+        dl = np.zeros((d, d))
+        dl[::8, ::8] = self.delta
+        self._q_row = torch.from_numpy(np.concatenate([luma, chroma, chroma]).astype(np.float64)).to(device)
+        self._delta_row = torch.from_numpy(np.concatenate([dl.reshape(-1), np.zeros(2 * d * d // n)])).to(device)
+        sites = d * d // n
+        if n == 1:                       # every pixel its own site: the three singular values of M
+            spectrum = np.concatenate([np.full(sites, v) for v in np.linalg.svd(self.matrix, compute_uv=False)])
+        else:
+            wn = float(np.sqrt((self.matrix[0] ** 2).sum()))
+            dc = np.linalg.svd(np.diag([1.0, n ** -0.5, n ** -0.5]) @ self.matrix, compute_uv=False)
+            spectrum = np.concatenate([np.full(sites * (n - 1), wn)] + [np.full(sites, v) for v in dc])
+        self._singulars = torch.from_numpy(np.sort(spectrum)[::-1].astype(np.float32)).to(device)
+
+    def mcus_per_workgroup(self):
+        """The launch geometry of the `*_jpeg_*` kernels: a workgroup of 256 threads owns 16 / rw consecutive MCUs."""
+        return 16 // self.rw
+
+    def workgroups(self, B):
+        mcus = B * (self.img_dim // (8 * self.rw)) * (self.img_dim // (8 * self.rh))
+        return -(-mcus // self.mcus_per_workgroup())
+
+    def measurement_size(self):
+        return self.img_dim ** 2 + 2 * (self.img_dim ** 2 // (self.rw * self.rh))
+
+    def measurement_image_shape(self):
+        return None                                                  # coefficient planes of two sizes: measurements are .npy rows
+
+    def singulars(self):
+        return self._singulars
+
+    def _geometry(self):
+        return self.img_dim, self.img_dim, self.rw, self.rh, self._m
+
+    def _rows_of(self, name, vec, *tail):
+        x = _img(vec, 3, self.img_dim)
+        B = x.shape[0]
+        y = torch.empty(B, self.measurement_size(), dtype=torch.float32, device=x.device)
+        ops.call(name, _p(x), _p(y), B, *self._geometry(), *tail)
+        return y
+
+    def A(self, vec):
+        """The encoder: the dequantised cell centres of T x."""
+        return self._rows_of("ddnm_op_jpeg_A_f32", vec, self._q, self.delta)
+
+    def A_linear(self, vec):
+        """T x, unquantised."""
+        return self._rows_of("ddnm_op_jpeg_T_f32", vec)
+
+    def A_pinv(self, vec):
+        y = _flat(vec)
+        B = y.shape[0]
+        if y.shape[1] != self.measurement_size():
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, this operator has {self.measurement_size()}")
+        x = torch.empty(B, 3 * self.img_dim ** 2, dtype=torch.float32, device=y.device)
+        ops.call("ddnm_op_jpeg_pinv_f32", _p(y), _p(x), B, *self._geometry())
+        return x
+
+    def levels(self, y):
+        """The integer quantisation levels rint((y - delta) / q) of measurement rows (int64; not on the sampler's path)."""
+        y = _flat(y)
+        if y.shape[1] != self.measurement_size():
+            raise ValueError(f"measurement rows have {y.shape[1]} entries, this operator has {self.measurement_size()}")
+        return torch.round((y.double() - self._delta_row.to(y.device)) / self._q_row.to(y.device)).long()
+
+    def _check_y(self, y, B):
+        if y.shape[0] != B or y.numel() != B * self.measurement_size():
+            raise ValueError(f"y must be [{B}, {self.measurement_size()}], got {tuple(y.shape)}")
+        return ops._f32c(y, "y")
+
+    def ddnm_step(self, xt, et, noise, y, s, x0_out, xt_next):
+        """One launch, one pass; x0_out (may be None) and xt_next must not be xt or et."""
+        B = xt.shape[0]
+        ops.step_call("ddnm_step_jpeg_f32", xt, et, noise, self._check_y(y, B), _p(x0_out), _p(xt_next), B,
+                      *self._geometry(), self._q, self.box, s)
+
+
 class GeneralA(A_functions):
     """svd_operators.py:173-208: an explicit dense measurement matrix A [m, d] with a full LAPACK SVD (torch.svd on the
     host, like the reference's constructor; singular values below 1e-3 are zeroed, :184-185).  Used by none of the `--deg`
@@ -1798,9 +1941,10 @@ def demosaic_pattern(deg, cfa_path="exp/cfa/pattern.npy"):
 
 
 def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask.npy", perm=None,
-                   cfa_path="exp/cfa/pattern.npy"):
+                   cfa_path="exp/cfa/pattern.npy", jpeg_box=None):
     """Operator factory of guided_diffusion/diffusion.py:451-523 for the --deg values on the hot path, and of the
-    demosaicing tasks (`demosaic_<cfa name>`, `demosaic`: deg_scale is ignored)."""
+    demosaicing tasks (`demosaic_<cfa name>`, `demosaic`: deg_scale is ignored).  `jpeg_box` (--jpeg_box) is the share of
+    the quantisation cell of `--deg jpeg_*`, JPEG_BOX when None."""
     c, d = config.data.channels, config.data.image_size
     if deg.startswith(DEMOSAIC):
         return Mosaic(c, d, demosaic_pattern(deg, cfa_path), device)
@@ -1850,7 +1994,24 @@ def build_operator(deg, deg_scale, config, device, mask_path="exp/inp_masks/mask
             raise ValueError(f"--deg chroma_sub takes --deg_scale {' | '.join(str(r) for r in CHROMA_SQUARE)} (square chroma "
                              f"sites), got {deg_scale!r}")
         return ChromaSubsample(c, d, int(deg_scale), int(deg_scale), device)
+    if deg in JPEG_NAMES:                                    # 4:4:4, 4:2:2, 4:2:0; --deg_scale is the quality
+        return JPEG(c, d, jpeg_quality_of(deg, deg_scale), *JPEG_NAMES[deg], device,
+                    box=JPEG_BOX if jpeg_box is None else jpeg_box)
     raise ValueError("degradation type not supported")
+
+
+JPEG_BOX = 0.98
+
+
+def jpeg_quality_of(deg, deg_scale):
+    """The integer quality of `--deg jpeg_* --deg_scale Q`; a ValueError that names the range otherwise."""
+    try:
+        ok = deg_scale is not None and float(deg_scale) == int(deg_scale) and 1 <= int(deg_scale) <= 100
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"--deg {deg} takes --deg_scale Q, the JPEG quality, an integer in 1..100: got {deg_scale!r}")
+    return int(deg_scale)
 
 
 def bicubic_kernel(factor):

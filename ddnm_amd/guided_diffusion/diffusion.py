@@ -49,7 +49,12 @@ Deliberate differences at the boundary (not in the results):
     `--deg chroma_sub --deg_scale 2 | 4 | 8` (square sites) restore a picture stored as Y'CbCr with subsampled chroma:
     full-resolution luma, one Cb and one Cr sample per site (svd_operators.ChromaSubsample, full-range BT.601: the exact
     pseudo-inverse, one fused step kernel for DDNM and one for DDNM+), so every switch above applies; a measurement is the
-    three planes in a row, S^2 + 2 S^2 / n values, which no picture holds (`.npy` rows), and `Apy_{i}.png` shows A^+ y.
+    three planes in a row, S^2 + 2 S^2 / n values, which no picture holds (`.npy` rows), and `Apy_{i}.png` shows A^+ y;
+  * `--deg jpeg_444 | jpeg_422 | jpeg_420 --deg_scale Q` (the quality, an integer in 1..100) restores a JPEG file
+    (svd_operators.JPEG): the measurement is the dequantised 8 x 8 block-DCT coefficients of those planes, the step pulls
+    T x0 back into every coefficient's quantisation cell (share `--jpeg_box`, default 0.98) in one fused launch, so the
+    restoration re-encodes to the same file (`Cons` is 0 exactly then); `Apy_{i}.png` is the decoded JPEG picture.
+    Noise-free only: `--sigma_y > 0`, `--sigma_y_shot`, `--sigma_y_map` and `--simplified` are refused (check_jpeg_flags).
 
 All of these run through ONE path of `Diffusion.svd_based_ddnm_plus`: the plan (`fuse_groups`: which loader batches this
 rank restores, grouped into sampler calls; `restored_images` is the same plan as image indices), `prepare` (a loader batch
@@ -69,8 +74,9 @@ from .. import dist as ddist
 from .. import ops
 from ..functions.svd_ddnm import (_AtenNoise, _reverse_loop, _TapeNoise, ddnm_diffusion, ddnm_plus_diffusion,
                                   get_schedule_jump)
-from ..functions.svd_operators import (DEMOSAIC, HN_OPERATORS, Colorization, Denoising, Inpainting, InpaintingBank,
-                                      NoiseModel, SuperResolution, build_operator, mask_color_sr, missing_indices_of_mask)
+from ..functions.svd_operators import (DEMOSAIC, HN_OPERATORS, JPEG_NAMES, Colorization, Denoising, Inpainting, InpaintingBank,
+                                      NoiseModel, SuperResolution, build_operator, jpeg_quality_of, mask_color_sr,
+                                      missing_indices_of_mask)
 from .models import Model
 
 
@@ -247,6 +253,29 @@ def check_noise_flags(args, simplified):
     if simplified and (float(getattr(args, "sigma_y_shot", 0.0) or 0.0) != 0.0 or getattr(args, "sigma_y_map", None)):
         raise ValueError("--simplified with --sigma_y_shot / --sigma_y_map: the simplified loop knows one sigma_y; "
                          "per-entry measurement noise runs on the SVD path only")
+
+
+def check_jpeg_flags(args, simplified):
+    """What `--deg jpeg_444 | jpeg_422 | jpeg_420` cannot be combined with, and `--jpeg_box` under any other --deg."""
+    box = getattr(args, "jpeg_box", None)
+    if args.deg not in JPEG_NAMES:
+        if box is not None:
+            raise ValueError(f"--jpeg_box is the cell share of --deg {' | '.join(JPEG_NAMES)}; --deg {args.deg} does not read it")
+        return
+    jpeg_quality_of(args.deg, args.deg_scale)
+    if box is not None and not 0.0 <= box <= 1.0:
+        raise ValueError(f"--jpeg_box is a share of the quantisation cell, in [0, 1]: got {box!r}")
+    why = ("the quantisation error of a JPEG file is bounded, not Gaussian, and its cell is the exact model: the step "
+           "projects into the cell and there is no DDNM+ form")
+    if float(args.sigma_y) > 0.0:
+        raise ValueError(f"--deg {args.deg} with --sigma_y {args.sigma_y}: {why}")
+    if float(getattr(args, "sigma_y_shot", 0.0) or 0.0) != 0.0:
+        raise ValueError(f"--deg {args.deg} with --sigma_y_shot: {why}")
+    if getattr(args, "sigma_y_map", None):
+        raise ValueError(f"--deg {args.deg} with --sigma_y_map: {why}")
+    if simplified:
+        raise ValueError(f"--simplified with --deg {args.deg}: the simplified loop corrects with A^+(A x0 - y) onto one "
+                         "value; the cell projection is a fused step of the SVD path only")
 
 
 def check_measurements(args, simplified):
@@ -799,6 +828,7 @@ class Diffusion(object):
         check_samples(samples(), simplified)
         check_measurements(self.args, simplified)
         check_noise_flags(self.args, simplified)
+        check_jpeg_flags(self.args, simplified)
         save_y()
         model = self._build_model()
         # batch sizes of 1 and 2 (the reference's shipped `sampling.batch_size: 1`) replay the forward from a hipGraph:
@@ -914,7 +944,7 @@ class Diffusion(object):
     def svd_based_ddnm_plus(self, model, cls_fn):
         args, config = self.args, self.config
         loader = self._loader()
-        A_funcs = build_operator(args.deg, args.deg_scale, config, self.device)
+        A_funcs = build_operator(args.deg, args.deg_scale, config, self.device, jpeg_box=getattr(args, "jpeg_box", None))
         # --path_y measurements:DIR: y is given, there is no x_orig; every file is checked against the operator here
         measured = isinstance(loader.dataset, MeasurementFolder)
         if measured:

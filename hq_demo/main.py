@@ -59,6 +59,10 @@ def main(conf, args):
     if str(args.get("path_y")).startswith("measurements:"):
         raise ValueError("--path_y measurements:DIR is read by the DDNM command line (main.py, SVD path) only: the "
                          "arbitrary-size demo degrades the picture --path_y names")
+    if str(args.get("deg")).startswith("jpeg_"):
+        raise ValueError(f"--deg {args.get('deg')}: JPEG restoration projects into quantisation cells in a fused step of the "
+                         "SVD path (main.py --deg jpeg_444 | jpeg_422 | jpeg_420 --deg_scale Q); hq_demo's shifted tiles "
+                         "do not line up with the 8 x 8 blocks of a file")
     print("Start", conf["name"])
     device = torch.device(conf.get("device") or "cuda")
     model, diffusion = create_model_and_diffusion(**select_args(conf, model_and_diffusion_defaults().keys()), conf=conf)

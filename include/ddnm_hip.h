@@ -32,7 +32,8 @@ int ddnm_version(void);                 /* ABI version, currently 7 (bumped on e
                                            per-image inpainting entry points *_pi_* were added under 7: new symbols
                                            only, no struct and no existing prototype changed; the demosaicing entry
                                            points *_mosaic_*, the old-photo ones *_mcsr_* and the chroma ones
-                                           *_chroma_* and the per-entry-noise ones *_hn_* likewise) */
+                                           *_chroma_*, the per-entry-noise ones *_hn_* and the JPEG ones *_jpeg_*
+                                           likewise) */
 const char* ddnm_build_digest(void);    /* sha256 of the sources + flags this binary was built from (build.py) */
 int ddnm_sizeof(int which);             /* sizeof of 0: ddnm_conv_desc, 1: ddnm_gemm_desc, 2: ddnm_conv16_desc,
                                            3: ddnm_step_scalars as compiled into the binary (-1: unknown index) */
@@ -893,6 +894,60 @@ int ddnm_step_plus_chroma_keyed_f32(const float* xt, const float* et, int64_t et
                                     const float* y, float* x0_out, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw,
                                     int32_t rh, const float* m9_host, float sigma_y, float sigma_t, float eta,
                                     const ddnm_step_scalars* s, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * JPEG-artifact restoration: the measurement is the quantisation CELL of every 8 x 8 block-DCT coefficient of the
+ * chroma-subsampled planes, and the range-space correction pulls T x0 back into the cell instead of onto one value.  The
+ * reference has no such operator; the entry points stand for A / A_pinv of its operator classes in the step of
+ * functions/svd_ddnm.py:57-65.  Added under ABI 7: new symbols only (csrc/jpeg.hip).
+ *   x [B][3][H][W], RGB, scale [-1, 1].  Site (rw, rh): (1,1) 4:4:4, (2,1) 4:2:2, (2,2) 4:2:0; H % (8 rh) == W % (8 rw) == 0.
+ *   M = m9_host: HOST pointer to the 3 x 3 colour matrix of the chroma section above (rows w_Y, w_Cb, w_Cr, invertible).
+ *   T (linear): the planes Y | Cb | Cr of ddnm_op_chroma_A_f32 (luma at every pixel, chroma averaged per site), then per
+ *       plane and per 8 x 8 block the orthonormal 2-D DCT-II  C X C^T,  C[k][n] = s_k cos((2n + 1) k pi / 16),
+ *       s_0 = sqrt(1/8), s_k = sqrt(2/8).  In place: coefficient (u, v) of block (I, J) sits at plane position
+ *       (8 I + u, 8 J + v); planes row-major in the row order [ Y | Cb | Cr ]: H W (1 + 2 / (rw rh)) entries per row, a
+ *       multiple of 4.  T has full row rank; T^+ = A_chroma^+ . IDCT is its exact Moore-Penrose inverse (an orthogonal
+ *       factor on the left does not change a pseudo-inverse).
+ *   q = q128_host: HOST pointer to 128 quantisation steps in x units (the 8-bit table entry / 127.5), luma [64] then
+ *       chroma [64], natural (row-major u, v) order, finite and > 0.
+ *   delta: the level shift.  An encoder subtracts 128 from 8-bit samples; on this scale that is the offset -4 / 127.5 on
+ *       the luma DC coefficient only, every other coefficient has offset 0.
+ *   A (the encoder):  y = q rint((T x - delta) / q) + delta, the dequantised cell centre (rint: ties to even).
+ *       A^+ y := T^+ y is what a decoder shows before clipping to 8 bit.
+ * One workgroup of 256 threads owns 16 / rw consecutive MCUs (8 rw x 8 rh pixels; MCUs numbered row-major over the batch);
+ * every MCU is transformed inside its workgroup, the 8-point transforms in registers and the two transposes of a block
+ * through LDS.  An image gives the same bits alone and inside any batch.
+ * NULL pointer (x0 of the step aside), B <= 0, no noise source, a misaligned key table, an output that is xt, et or the
+ * other output, a singular M, a step q that is not finite or <= 0, box outside [0, 1]: DDNM_E_BADARG; then a site not
+ * listed, H or W <= 0, H % (8 rh), W % (8 rw) or et_bstride % 4 != 0: DDNM_E_SHAPE.  All of it is checked before any launch.
+ * ------------------------------------------------------------------------- */
+/* libjpeg's tables for quality 1..100, host only (no device call): scale = 5000 / quality (integer) below 50, else
+ * 200 - 2 quality; entry = clamp((base * scale + 50) / 100, 1, 255) with base the tables K.1 / K.2 of ITU-T T.81 Annex K;
+ * q128_out[i] = entry / 127.5 (luma, then chroma, natural order); *delta_out = dc_shift ? -4 / 127.5 : 0.
+ * NULL pointer or quality outside 1..100: DDNM_E_BADARG. */
+int ddnm_jpeg_quality_tables(int32_t quality, int32_t dc_shift, float* q128_out, float* delta_out);
+/* c = T x;  y = A x (the encoder);  x = T^+ y */
+int ddnm_op_jpeg_T_f32(const float* x, float* c, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                       const float* m9_host, void* stream);
+int ddnm_op_jpeg_A_f32(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                       const float* m9_host, const float* q128_host, float delta, void* stream);
+int ddnm_op_jpeg_pinv_f32(const float* y, float* x, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                          const float* m9_host, void* stream);
+/* Fused step in ONE launch and one pass, with h = box q / 2, 0 <= box <= 1:
+ *   x0 = (xt - et * sqrt_1m_at) / sqrt_at;   c = T x0;   x0h = x0 - lambda * T^+(c - clamp(c, y - h, y + h));
+ *   xt' = sqrt_at_next * x0h + c1 * noise + c2 * et.
+ * box = 0 is x0 - lambda T^+(T x0 - y); with box just below 1 (0.98: clamped coefficients land on the cell edge, and the
+ * margin keeps fp32 rounding from deciding how they re-quantise) A xt' at the last step returns the measured levels.
+ * x0 (optional) receives the uncorrected x0, bit for bit that of ddnm_step_x0_f32; noise as in ddnm_step_chroma_f32 /
+ * _keyed_f32, indexed by the pixel's linear position in the tensor.  xt, et, noise and y are read once, x0 and xt_next
+ * written once; no global scratch.  x0 and xt_next must not be xt or et (checked for identity). */
+int ddnm_step_jpeg_f32(const float* xt, const float* et, int64_t et_bstride, const float* noise, const float* y, float* x0,
+                       float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh, const float* m9_host,
+                       const float* q128_host, float box, const ddnm_step_scalars* s, void* stream);
+int ddnm_step_jpeg_keyed_f32(const float* xt, const float* et, int64_t et_bstride, const uint32_t* rng_keys, const float* y,
+                             float* x0, float* xt_next, int32_t B, int32_t H, int32_t W, int32_t rw, int32_t rh,
+                             const float* m9_host, const float* q128_host, float box, const ddnm_step_scalars* s,
+                             void* stream);
 
 /* ------------------------------------------------------------------------- *
  * hq_demo sampler: DDPM posterior step with the DDNM core and the mask-shift tiles

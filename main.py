@@ -38,7 +38,7 @@ FLAGS = [
     (("--config",), dict(type=str, required=True, help="YAML under configs/ (or an absolute path)")),
     (("--seed",), dict(type=int, default=1234, help="seed of torch / numpy / the device generator")),
     (("--exp",), dict(type=str, default="exp", help="root of the run directory (<exp>/image_samples, <exp>/datasets, <exp>/logs)")),
-    (("--deg",), dict(type=str, required=True, help="degradation operator, e.g. sr_bicubic, colorization, inpainting, cs_walshhadamard, deblur_gauss, demosaic_rggb, mask_color_sr (old photo: exp/inp_masks/mask.npy, grey, --deg_scale 1 | 2 | 4 | 8), sr_color (the same without a mask), chroma_420 | chroma_422 | chroma_411 (full luma, subsampled chroma), chroma_sub (square chroma sites of --deg_scale 2 | 4 | 8)")),
+    (("--deg",), dict(type=str, required=True, help="degradation operator, e.g. sr_bicubic, colorization, inpainting, cs_walshhadamard, deblur_gauss, demosaic_rggb, mask_color_sr (old photo: exp/inp_masks/mask.npy, grey, --deg_scale 1 | 2 | 4 | 8), sr_color (the same without a mask), chroma_420 | chroma_422 | chroma_411 (full luma, subsampled chroma), chroma_sub (square chroma sites of --deg_scale 2 | 4 | 8), jpeg_444 | jpeg_422 | jpeg_420 (a JPEG file of quality --deg_scale 1..100)")),
     (("--path_y",), dict(type=str, required=True, help="dataset sub-folder below <exp>/datasets, synthetic:N, or measurements:DIR (given measurements, no ground truth)")),
     (("--sigma_y",), dict(type=float, default=0.0, help="std of the measurement noise on the [0,1] scale (> 0 selects DDNM+)")),
     (("--eta",), dict(type=float, default=0.85, help="eta of the DDIM-style update")),
@@ -56,6 +56,8 @@ FLAGS = [
 ENGINE_FLAGS = [
     (("--sigma_y_shot",), dict(type=float, default=0.0, help="shot-noise gain g >= 0 on the [0,1] scale: Var = sigma_y^2 + g * intensity per measured entry (--deg demosaic_* and denoising)")),
     (("--sigma_y_map",), dict(type=str, default=None, help="FILE.npy with the std of every measurement entry on the [0,1] scale, one row shared by all images (--deg demosaic_* and denoising; --sigma_y must be 0 or unset)")),
+    # the quantisation-cell projection of --deg jpeg_444 | jpeg_422 | jpeg_420 (--deg_scale Q: the quality, 1..100)
+    (("--jpeg_box",), dict(type=float, default=None, help="share of the quantisation cell the JPEG step projects onto, in [0, 1] (default 0.98; 0: the cell centre, plain DDNM; --deg jpeg_* only)")),
 ]
 
 

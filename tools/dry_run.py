@@ -16,7 +16,7 @@ from ddnm_amd import _lib, ops  # noqa: E402
 
 HOST_ONLY = ("_supported", "_stats_tiles", "_workspace_floats", "_nchunk", "_tile_n", "_fuses_skip", "_fuses_fin",
              "_persistent", "_act_scale", "ddnm_version", "ddnm_error_string", "ddnm_build_digest", "ddnm_sizeof",
-             "ddnm_chroma_constants")
+             "ddnm_chroma_constants", "ddnm_jpeg_quality_tables")
 
 
 class DryLib:
